@@ -2,12 +2,17 @@
 """Benchmark of the HVAE train step (and the counterfactual loop) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W            # N=1 directly, N>1 under torch.distributed.run
+    python bench.py ... --full                               # + everything beyond the headline (see below)
+    python bench.py ... --dump-outputs DIR                   # + what the last timed step computed, as DIR/*.npy
 
 A "step" is one pass of the hot path over one synthetic batch already resident in HBM: weight images -> HVAE forward
 -> hand-written backward -> (DP: RCCL gradient all-reduce) -> grad-norm / clip / skip -> fused AdamW + EMA.
-Prints ONE JSON line on rank 0 (contract in the task description) with the `roofline` of the dominant kernel class
-(measured live with HIP events on the launch stream over one profiled step of the same workload) and the
-`cpu_baseline` (the oracle = bit-matched restatement of the reference's PyTorch-CPU path, timed on this host).
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times the K steps and
+prints the headline (images/s, ms_per_step).  With --full the same line also carries the `roofline` of the dominant
+kernel class (measured live with HIP events on the launch stream over one profiled step of the same workload),
+`launches_per_step`, the counterfactual loop, the f32 parity leg, the other configs, the batch sweep, the bandwidth
+kernels and the `cpu_baseline` (the oracle = bit-matched restatement of the reference's PyTorch-CPU path, timed on this
+host); --no-cpu / --no-cf / --no-f32 / --no-extra drop parts of that.
 """
 import argparse
 import json
@@ -29,6 +34,7 @@ CF_GFLOP = {"morphomnist": 0.185, "cmnist": 0.192, "ukbb192": 47.67, "mimic192":
 # 23.06+12.31 / 9.12+5.22 / 12.45+7.13 GFLOP)
 CF_GFLOP_REUSE = {"morphomnist": 0.135, "cmnist": 0.141, "ukbb192": 35.37, "mimic192": 14.34, "mimic224": 19.58}
 MFMA_PEAK_TF = {"f32": 157.3, "f16": 2500.0}  # dense, MI355X_MICROARCH.md
+DUMP_SAMPLE = 1 << 22  # parameters per --dump-outputs array (16 MB of float32); larger models are sampled
 
 
 def synth_batch(name, hp, B, device, seed):
@@ -123,6 +129,24 @@ def cpu_baseline(name, budget_s=8.0, hard_limit_s=75.0):
     return dict(value=best[0], unit="images/s", cores=best[1], kind="port", images_s_by_threads=tried, host_threads=ncpu,
                 sample=f"{best[2]} train steps of {name} at batch {best[3]} (fwd+bwd+clip+AdamW+EMA), f32, after 1 warm-up step, "
                        f"best of {sorted(int(k) for k in tried)} torch threads (one child process each)")
+
+
+def dump_outputs(path, out, model, ema_model):
+    """--dump-outputs: what the caller of the timed step holds after the last timed step, as float32 .npy files --
+    `elbo_nll_kl` (the step's return value), `params` and `ema_params` (the trained and the EMA weights, concatenated in
+    parameters() order).  Above DUMP_SAMPLE weights both weight arrays hold the same fixed, seeded, sorted sample."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "elbo_nll_kl.npy"), out.detach().float().cpu().numpy())
+    idx = None
+    for name, mod in (("params", model), ("ema_params", ema_model)):
+        if mod is None:
+            continue
+        flat = torch.cat([p.detach().reshape(-1).float() for p in mod.parameters()])
+        if idx is None and flat.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+        np.save(os.path.join(path, name + ".npy"), (flat if idx is None else flat[idx.to(flat.device)]).cpu().numpy())
 
 
 def _code_tree_sha():
@@ -487,11 +511,15 @@ def main():
     ap.add_argument("--dtype", default="f16", choices=["f32", "f16"])
     ap.add_argument("--dmol", action="store_true", help="DMoL likelihood head (cmnist)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-cf", action="store_true")
-    ap.add_argument("--no-f32", action="store_true", help="skip the f32 parity-path leg (default: timed after the f16 headline at N=1)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other BASELINE configs, the batch sweep and the bandwidth-kernel table (default ukbb192 run only)")
+    ap.add_argument("--full", action="store_true", help="after the headline also measure the roofline, the counterfactual loop, the f32 parity "
+                                                         "leg, the other configs, the batch sweep, the bandwidth kernels and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-cf", action="store_true", help="(--full) skip the counterfactual loop")
+    ap.add_argument("--no-f32", action="store_true", help="(--full) skip the f32 parity-path leg (timed after the f16 headline at N=1)")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the other BASELINE configs, the batch sweep and the bandwidth-kernel table (default ukbb192 run only)")
     ap.add_argument("--prep-steps", type=int, default=20, help="untimed optimiser steps so the prior heads are non-zero")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (ELBO / NLL / KL, trained and EMA weights) as DIR/*.npy")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -562,11 +590,13 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, m, ts.ema_model)  # (before anything below steps the model again)
     elbo, nll, kl = [float(v) for v in out.cpu()]
     stats = ts.stats()
     img_s = B * world * a.steps / dt
     # the profiled eager step contains the gradient all-reduce: every rank takes part (rank 0 reports)
-    roof = profile_step(ts, x, pa, a.dtype, (a.config, B))
+    roof = profile_step(ts, x, pa, a.dtype, (a.config, B)) if a.full else None
 
     if rank == 0:
         gf = TRAIN_GFLOP_PER_IMG[a.config]
@@ -580,7 +610,7 @@ def main():
                        "hipgraph": not a.no_graph, "params": sum(p.numel() for p in m.parameters())},
             "elbo_nats_per_dim": elbo, "nll": nll, "kl": kl, "opt_steps": stats["opt_steps"], "skipped": stats["n_skipped"],
             "wgrad_partial_bytes_per_step": sum(e[0].numel() * 4 for e in ts.eng._partials.values()),
-            "arena_bytes": ts.eng.arena.high_water, "launches_per_step": roof.get("launches_per_step"),
+            "arena_bytes": ts.eng.arena.high_water,
             "model_tflops": img_s * gf * 1e9 / 1e12,
             "model_mfma_frac": img_s * gf * 1e9 / 1e12 / (MFMA_PEAK_TF[a.dtype] * world),
             "param_abs_sum": float(sum(p.detach().double().abs().sum() for p in m.parameters())),
@@ -600,8 +630,10 @@ def main():
                          "backend": os.environ.get("CGEN_DIST_BACKEND", "nccl"),
                          ("rccl_ranks_seen" if os.environ.get("CGEN_DIST_BACKEND", "nccl") == "nccl" else "gloo_ranks_seen"): ranks_seen,
                          "devices_visible": torch.cuda.device_count()}
-        res["roofline"] = roof
-        if not a.no_cf:
+        if a.full:
+            res["launches_per_step"] = roof.get("launches_per_step")
+            res["roofline"] = roof
+        if a.full and not a.no_cf:
             # top-level counterfactuals_per_s = the loop that meets north_star's 1e-3 absolute on the reference-made fixtures
             # (tests/test_gpu_fullsize.py): f32 storage (cf_path says which MFMAs).  The all-16-bit loop is reported beside it
             # as `f16_loop`, labelled with the bound it is held to (5e-3) and its deviation on this batch.
@@ -619,9 +651,9 @@ def main():
                                    "vs_f32_cf_maxabs_this_batch": cf_deviation(ts.ema_model, m32cf, x, pa)}
             del m32cf
             torch.cuda.empty_cache()
-        if world == 1 and a.dtype == "f16" and not a.no_f32:
+        if a.full and world == 1 and a.dtype == "f16" and not a.no_f32:
             res["f32"] = f32_leg(a, hp, B, dev, x, pa, m)
-        if world == 1 and not a.no_extra and a.config == "ukbb192" and a.batch is None and a.dtype == "f16":
+        if a.full and world == 1 and not a.no_extra and a.config == "ukbb192" and a.batch is None and a.dtype == "f16":
             # the other BASELINE.json configs and a per-GPU batch sweep of the headline model, same process, same code
             del ts
             torch.cuda.empty_cache()
@@ -644,7 +676,7 @@ def main():
                                     "f16_loop_pixel_bound_held_vs_reference": 5e-3,
                                     "note": "counterfactuals_per_s at top level is the loop that meets north_star's 1e-3 on the reference-made "
                                             "fixtures (f32 storage); f16_loop is the all-16-bit approximation, a 5e-3 number on those fixtures"}}
-        if world == 1 and not a.no_cpu:
+        if a.full and world == 1 and not a.no_cpu:
             res["cpu_baseline"] = cpu_baseline(a.config)
         print(json.dumps(res))
     if distributed:

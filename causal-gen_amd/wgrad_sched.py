@@ -1,6 +1,7 @@
 """Weight-gradient scheduling of the engine (a mixin of `Engine`): every weight gradient of a backward pass is a leaf, so they are
 deferred, planned once as horizontally batched launches (`cgen_conv2d_wgrad_batch_plan / _run`: one launch walks the record list
-of all pending problems), flushed in the background of the backward chain on a side stream with a capped grid, and their split-K
+of all pending problems), flushed at a mark of the backward chain with a capped grid -- in line on the main stream by default,
+on a side stream beside the chain with CGEN_WGRAD_BG_SERIAL=0 (LABNOTES 12) -- and their split-K
 partials reduced by multi-tensor launches (`cgen_wgrad_reduce`) in rounds with at most one event per conv site.  DESIGN.md 3.3.
 (reference: what `loss.backward()` does for the conv weights in trainer.py:64-67)"""
 import ctypes as C
@@ -164,7 +165,10 @@ class WgradMixin:
             for i in rest:
                 self.lib.conv2d_wgrad(C.byref(args[i]), self.stream)
                 self.launches += 1
-            if os.environ.get("CGEN_WGRAD_BG_SERIAL"):  # debugging: same launches, but in line on the main stream
+            # In line on the main stream by default: running beside the backward chain (CGEN_WGRAD_BG_SERIAL=0) the flushed batch
+            # now and then leaves a non-finite activation gradient in the encoder's chain (LABNOTES 12: only with cgen_block3 on), so
+            # the same arguments did not give the same training run twice
+            if os.environ.get("CGEN_WGRAD_BG_SERIAL", "1") != "0":
                 side = main
             else:
                 side.wait_stream(main)

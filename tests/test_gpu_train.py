@@ -267,7 +267,7 @@ def test_dp_bench_path_two_gloo_ranks_on_one_gpu(launcher):
     env = dict(os.environ, CGEN_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    args = ["--gpus", "2", "--config", "morphomnist", "--batch", "16", "--steps", "2", "--warmup", "1", "--prep-steps", "1", "--no-cf"]
+    args = ["--gpus", "2", "--config", "morphomnist", "--batch", "16", "--steps", "2", "--warmup", "1", "--prep-steps", "1", "--no-cf", "--full"]
     if launcher == "self":
         cmd = [sys.executable, os.path.join(root, "bench.py")] + args
     else:
@@ -313,7 +313,19 @@ def test_dp_allreduce_overlapped_with_backward_equals_the_serialized_exchange():
 def test_backward_is_bit_reproducible_next_to_the_background_weight_gradient_kernel():
     """Three backward passes of the ukbb192 model (bf16, background flush on) from identical state must give bit-identical
     gradients.  They did not while packed-f32 instructions were in the kernels: a co-resident MFMA wave of the background
-    weight-gradient kernel corrupts them (tools/coexec_probe.py); build.sh keeps them out of every kernel."""
+    weight-gradient kernel corrupts them (tools/coexec_probe.py); build.sh keeps them out of every kernel.  The flush runs in
+    line by default (LABNOTES 12): CGEN_WGRAD_BG_SERIAL=0 puts it back on its side stream, beside the backward chain, here."""
+    import os
+    import sys
+
+    os.environ["CGEN_WGRAD_BG_SERIAL"] = "0"
+    try:
+        _bit_reproducible_next_to_the_background_flush()
+    finally:
+        del os.environ["CGEN_WGRAD_BG_SERIAL"]
+
+
+def _bit_reproducible_next_to_the_background_flush():
     import os
     import sys
 
@@ -366,6 +378,29 @@ def test_backward_is_bit_reproducible_next_to_the_background_weight_gradient_ker
     bad = [n for n, p in m.named_parameters() if p.grad is not None and not torch.equal(runs[0][n], p.grad)]
     assert not bad, ("paired data-gradient launches differ from single ones", len(bad), bad[:4])
     eng.blk3_pair = eng.conv_pair = True
+
+
+def test_default_train_steps_keep_finite_gradients():
+    """LABNOTES 12: with the weight-gradient flush beside the backward chain, 4-8 of 2500 ukbb192 train steps (B=32) dropped a
+    non-finite gradient the same run did not produce again, so two runs with the same arguments trained differently.  The
+    default in-line flush must keep every step of that run finite: a gradient left non-finite is counted in state[6]."""
+    import os
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from causal_gen_amd.train import TrainStep
+
+    assert os.environ.get("CGEN_WGRAD_BG_SERIAL", "1") != "0"
+    m, hp = bench.build_model("ukbb192", "f16")
+    m = m.cuda()
+    ts = TrainStep(m, hp, ema=True)
+    x, pa = bench.synth_batch("ukbb192", hp, 32, "cuda", seed=100)
+    for _ in range(2500):
+        ts.step(x, pa)
+    st = ts.state.cpu().tolist()
+    assert st[6] == 0 and st[4] == 0, ("non-finite gradients", st[6], "skipped", st[4])
 
 
 def test_full_size_bf16_path_agrees_with_the_f32_parity_path():

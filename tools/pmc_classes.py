@@ -2,7 +2,7 @@
 """Per kernel CLASS summary of the two instruction-mix PMC passes (tools/pmc_insts.sh): MFMA-pipe busy share and instructions per
 MFMA.  mfma_busy_pct_of_wave_lifetime = SQ_VALU_MFMA_BUSY_CYCLES / (4 x SQ_WAVE_CYCLES) (the guide: MFMA_BUSY counts cycles,
 WAVE_CYCLES quad-cycles): the share of a wave's resident time its SIMD's matrix pipe was busy -- an UPPER bound on the pipe's
-utilisation when several waves share a SIMD.   usage: pmc_classes.py gpurun_out/<tag>"""
+utilisation when several waves share a SIMD.   usage: pmc_classes.py profile_out/<tag>"""
 import collections
 import csv
 import json

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel instruction mix from the two passes of tools/pmc_insts.sh: per-wave VALU / SALU / LDS / VMEM / MFMA counts.
-usage: pmc_insts.py gpurun_out/<tag>  [substring filter]"""
+usage: pmc_insts.py profile_out/<tag>  [substring filter]"""
 import collections
 import csv
 import sys

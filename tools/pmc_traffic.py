@@ -36,7 +36,7 @@ def main():
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from tree_sha import tree_sha
     out["_source"] = {"code_tree_sha": tree_sha(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
-                      "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --steps 2 --warmup 1 --prep-steps 1 --no-cpu --no-cf --no-f32 --no-extra"}
+                      "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python bench.py --full --steps 2 --warmup 1 --prep-steps 1 --no-cpu --no-cf --no-f32 --no-extra"}
     print(json.dumps(out, indent=1))
     if len(sys.argv) > 3:
         json.dump(out, open(sys.argv[3], "w"), indent=1)
