@@ -136,8 +136,10 @@ PROTOTYPES = {
     "cgen_dmol_nll_fwd": [i32, i32, i32, i32, View, View, vp, vp],
     "cgen_dmol_nll_bwd": [i32, i32, i32, i32, View, View, vp, i32, View, vp],
     "cgen_dmol_decode": [i32, i32, i32, i32, View, i32, vp, u32, f32, vp, vp, vp],
+    "cgen_dmol_decode_bwd": [i32, i32, i32, i32, View, i32, vp, u32, f32, vp, vp, f32, View, vp],
     "cgen_elbo_finalize": [i32, vp, i32, f32, vp, i32, f32, f32, vp, vp, vp],
     "cgen_cf_dgauss_bwd": [i32, i32, i32, i32, i32, View, View, View, vp, f32, View, View, vp],
+    "cgen_cf_dmol_bwd": [i32, i32, i32, i32, i32, View, View, View, vp, f32, View, View, vp],
     "cgen_cf_pixels": [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "cgen_sumsq_partial": [vp, i64, vp, i32, vp],
     "cgen_clip_decide": [vp, i32, vp, f32, f32, vp, vp],
@@ -147,7 +149,7 @@ PROTOTYPES = {
     "cgen_rng_advance": [vp, u64, vp],
 }
 _RESTYPES = {"cgen_last_error": C.c_char_p}
-ABI_VERSION = 407  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
+ABI_VERSION = 408  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
 _NOCHECK = {"cgen_version", "cgen_h16_format", "cgen_last_error", "cgen_conv2d_wgrad_plan", "cgen_reparam_kl_chunks", "cgen_like_chunks",
             "cgen_block3_supported", "cgen_block4_supported", "cgen_block4_pair_supported", "cgen_block3_pair_supported", "cgen_conv2d_pair_supported", "cgen_stem_conv_supported"}
 

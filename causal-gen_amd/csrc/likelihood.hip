@@ -1,5 +1,6 @@
-// Likelihood kernels: discretised Gaussian (vae.py:352-422), discretised mixture of logistics (dmol.py), ELBO
-// assembly (vae.py:450-457) and the counterfactual pixel step (dscm.py:55-63).  All f32 math; HBM-bound.
+// Likelihood kernels: discretised Gaussian (vae.py:352-422), discretised mixture of logistics (dmol.py: loss, mean / sample
+// decode and their backward passes), ELBO assembly (vae.py:450-457) and the counterfactual pixel step (dscm.py:55-63) with
+// its backward over either head.  All f32 math; HBM-bound.
 #include "common.h"
 
 namespace cgen {
@@ -489,6 +490,152 @@ __global__ __launch_bounds__(256) void dmol_nll_bwd_kernel(DmP p) {
   }
 }
 
+// Philox words of one pixel for the sample mode: counters gi*4 + {0, 1, 2}.  Mixture m's Gumbel uniform is word m of
+// r | r2 | r3; the three logistic draws take r3[2], r3[3] and r2[3] ^ 0x9E3779B9.
+struct DmWords {
+  uint32_t r[4], r2[4], r3[4];
+};
+
+__device__ __forceinline__ void dm_words(uint64_t seed, uint64_t off, uint32_t stream_id, int64_t gi, DmWords& wd) {
+  Philox::gen(seed, off, stream_id, (uint64_t)gi * 4 + 0, wd.r);
+  Philox::gen(seed, off, stream_id, (uint64_t)gi * 4 + 1, wd.r2);
+  Philox::gen(seed, off, stream_id, (uint64_t)gi * 4 + 2, wd.r3);
+}
+
+// What the backward of one pixel's decode needs besides the logits themselves.
+struct DmDec {
+  float sel[DM_NMIX];  // selection weights: softmax over the kept mixtures, or one-hot
+  float pre[3];        // values entering the three sequential RGB clamps
+  float co[3];         // mixed tanh coefficients (g <- r, b <- r, b <- g)
+  float s[3];          // mixed log-scales before the -7 floor
+  float nz[3];         // logistic draw log u - log(1 - u) of the sample mode (0 for the means)
+};
+
+__device__ __forceinline__ float dm_unif(uint32_t r) { return 1e-5f + (1.f - 2e-5f) * Philox::u01(r); }
+__device__ __forceinline__ float clamp1(float v) { return fminf(fmaxf(v, -1.f), 1.f); }
+
+// One pixel of cgen_dmol_decode (dmol.py:121-215): selection weights (mode 0 soft, 1 hard, 10 + k top-k; kSample: the
+// Gumbel-max of mode 2), mixed parameters, the logistic draw at temperature logt (kSample), sequential RGB clamp.  Top-k
+// switches l[0..9] below the k-th largest to -inf in place.  Register arrays are indexed statically after unrolling: the
+// top-k threshold and the arg-max are picked by comparison, never by a runtime index (which would put l[] in scratch).
+template <bool kSample>
+__device__ __forceinline__ void dm_decode_px(float (&l)[100], int mode, const DmWords& wd, float logt, DmDec& d, float (&xs)[3],
+                                             float (&sc)[3]) {
+  if (!kSample && mode >= 10) {  // top-k (dmol.py:178-188): logits below the k-th largest are switched off, then renormalised
+    const int k = mode - 10;
+    float srt[DM_NMIX];
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) srt[m] = l[m];
+#pragma unroll
+    for (int a = 1; a < DM_NMIX; ++a)  // insertion sort, descending
+#pragma unroll
+      for (int b2 = a; b2 > 0; --b2)
+        if (srt[b2] > srt[b2 - 1]) { const float tmp = srt[b2]; srt[b2] = srt[b2 - 1]; srt[b2 - 1] = tmp; }
+    float thr = srt[0];
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) if (m == k - 1) thr = srt[m];
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) if (l[m] < thr) l[m] = -INFINITY;
+  }
+  if (!kSample && (mode == 0 || mode >= 10)) {  // soft: softmax weights (dmol.py:170-172)
+    float mx = -INFINITY, se = 0.f;
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) mx = fmaxf(mx, l[m]);
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) se += expf(l[m] - mx);
+    const float lse = mx + logf(se);
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) d.sel[m] = expf(l[m] - lse);
+  } else {
+    int am = 0;
+    float best = -INFINITY;
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) {
+      float v = l[m];
+      if (kSample) {  // Gumbel-max with uniforms in [1e-5, 1-1e-5] (dmol.py:128-129)
+        const uint32_t rr = m < 4 ? wd.r[m] : (m < 8 ? wd.r2[m - 4] : wd.r3[m - 8]);
+        v -= logf(-logf(dm_unif(rr)));
+      }
+      if (v > best) { best = v; am = m; }
+    }
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) d.sel[m] = (m == am) ? 1.f : 0.f;
+  }
+  float mu[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float a = 0.f, s = 0.f, k = 0.f;
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) {
+      a += l[10 + 30 * c + m] * d.sel[m];
+      s += l[10 + 30 * c + 10 + m] * d.sel[m];
+      k += tanhf(l[10 + 30 * c + 20 + m]) * d.sel[m];
+    }
+    mu[c] = a; d.s[c] = s; d.co[c] = k;
+    float ls = fmaxf(s, DM_MIN_LS);
+    d.nz[c] = 0.f;
+    if (kSample) {
+      ls += logt;
+      const float u = dm_unif(c == 0 ? wd.r3[2] : (c == 1 ? wd.r3[3] : wd.r2[3] ^ 0x9E3779B9u));
+      d.nz[c] = logf(u) - logf(1.f - u);
+      mu[c] += expf(ls) * d.nz[c];
+    }
+    sc[c] = expf(ls);
+  }
+  d.pre[0] = mu[0];
+  xs[0] = clamp1(d.pre[0]);
+  d.pre[1] = mu[1] + d.co[0] * xs[0];
+  xs[1] = clamp1(d.pre[1]);
+  d.pre[2] = mu[2] + d.co[1] * xs[0] + d.co[2] * xs[1];
+  xs[2] = clamp1(d.pre[2]);
+}
+
+// Backward of dm_decode_px: gx / gsc = d/d x and d/d scale of the three channels; writes d/d logits, all 100 channels, to go.
+// Conventions are torch autograd's over oracle/dmol_ref.py: a clamp to [-1, 1] passes the gradient on the closed interval,
+// the -7 log-scale floor passes iff s >= -7, tanh' = 1 - tanh^2.  (The reference writes the floor as const_max, which splits
+// the gradient in half at an exact tie: a measure-zero difference, not reproduced.)  The selection is a constant for the
+// hard mean and the sample, so the mixture logits get 0; soft / top-k take the softmax backward over the weights the
+// forward used, so switched-off mixtures get exactly 0.
+template <typename T, bool kSample>
+__device__ __forceinline__ void dm_decode_bwd_px(const float (&l)[100], int mode, const DmDec& d, float logt, const float (&gx)[3],
+                                                 const float (&gsc)[3], T* go) {
+  auto in = [](float v) { return (v >= -1.f && v <= 1.f) ? 1.f : 0.f; };
+  const float x0 = clamp1(d.pre[0]), x1 = clamp1(d.pre[1]);
+  float gmu[3], gs[3], gk[3];  // d/d (mixed mean + noise), d/d raw mixed log-scale, d/d mixed coefficient
+  gmu[2] = gx[2] * in(d.pre[2]);
+  gk[1] = gmu[2] * x0;
+  gk[2] = gmu[2] * x1;
+  gmu[1] = (gx[1] + gmu[2] * d.co[2]) * in(d.pre[1]);
+  gk[0] = gmu[1] * x0;
+  gmu[0] = (gx[0] + gmu[2] * d.co[1] + gmu[1] * d.co[0]) * in(d.pre[0]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float sc = expf(fmaxf(d.s[c], DM_MIN_LS) + (kSample ? logt : 0.f));
+    const float g = kSample ? gsc[c] + gmu[c] * d.nz[c] : gsc[c];  // x = mu + scale * nz
+    gs[c] = d.s[c] >= DM_MIN_LS ? g * sc : 0.f;
+  }
+  float gsel[DM_NMIX];
+#pragma unroll
+  for (int m = 0; m < DM_NMIX; ++m) gsel[m] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int m = 0; m < DM_NMIX; ++m) {
+      const float t = tanhf(l[10 + 30 * c + 20 + m]);
+      gsel[m] += gmu[c] * l[10 + 30 * c + m] + gs[c] * l[10 + 30 * c + 10 + m] + gk[c] * t;
+      Elem<T>::st(go + 10 + 30 * c + m, gmu[c] * d.sel[m]);
+      Elem<T>::st(go + 10 + 30 * c + 10 + m, gs[c] * d.sel[m]);
+      Elem<T>::st(go + 10 + 30 * c + 20 + m, gk[c] * d.sel[m] * (1.f - t * t));
+    }
+  }
+  const bool soft = !kSample && (mode == 0 || mode >= 10);
+  float dot = 0.f;
+#pragma unroll
+  for (int m = 0; m < DM_NMIX; ++m) dot += d.sel[m] * gsel[m];
+#pragma unroll
+  for (int m = 0; m < DM_NMIX; ++m) Elem<T>::st(go + m, soft ? d.sel[m] * (gsel[m] - dot) : 0.f);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void dmol_decode_kernel(int n, int h, int w, View logits, int mode, const uint64_t* rng,
                                                           uint32_t stream_id, float logt, float* xo, float* so) {
@@ -498,86 +645,95 @@ __global__ __launch_bounds__(256) void dmol_decode_kernel(int n, int h, int w, V
   if (mode == 2) { seed = rng[0]; off = rng[1]; }
   for (int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x; gi < total; gi += (int64_t)gridDim.x * 256) {
     const int b = (int)(gi / npix), px = (int)(gi % npix);
-    float l[100];
+    float l[100], xs[3], sc[3];
     dm_load<T>(vptr<T>(logits, b, px / w, px % w), l);
-    float sel[DM_NMIX];
-    uint32_t r[4] = {0, 0, 0, 0}, r2[4] = {0, 0, 0, 0}, r3[4] = {0, 0, 0, 0};
-    if (mode >= 10) {  // top-k (dmol.py:178-188): logits below the k-th largest are switched off, then renormalised
-      const int k = mode - 10;
-      float srt[DM_NMIX];
-#pragma unroll
-      for (int m = 0; m < DM_NMIX; ++m) srt[m] = l[m];
-#pragma unroll
-      for (int a = 1; a < DM_NMIX; ++a)  // insertion sort, descending
-#pragma unroll
-        for (int b2 = a; b2 > 0; --b2)
-          if (srt[b2] > srt[b2 - 1]) { const float tmp = srt[b2]; srt[b2] = srt[b2 - 1]; srt[b2 - 1] = tmp; }
-      float thr = srt[0];
-#pragma unroll
-      for (int m = 0; m < DM_NMIX; ++m) if (m == k - 1) thr = srt[m];
-#pragma unroll
-      for (int m = 0; m < DM_NMIX; ++m) if (l[m] < thr) l[m] = -INFINITY;
-    }
-    if (mode == 0 || mode >= 10) {  // soft: softmax weights (dmol.py:170-172)
-      float mx = -INFINITY, se = 0.f;
-#pragma unroll
-      for (int m = 0; m < DM_NMIX; ++m) mx = fmaxf(mx, l[m]);
-#pragma unroll
-      for (int m = 0; m < DM_NMIX; ++m) se += expf(l[m] - mx);
-      const float lse = mx + logf(se);
-#pragma unroll
-      for (int m = 0; m < DM_NMIX; ++m) sel[m] = expf(l[m] - lse);
-    } else {
-      if (mode == 2) {  // Gumbel-max with uniforms in [1e-5, 1-1e-5] (dmol.py:128-129)
-        Philox::gen(seed, off, stream_id, (uint64_t)gi * 4 + 0, r);
-        Philox::gen(seed, off, stream_id, (uint64_t)gi * 4 + 1, r2);
-        Philox::gen(seed, off, stream_id, (uint64_t)gi * 4 + 2, r3);
-      }
-      int am = 0;
-      float best = -INFINITY;
-#pragma unroll
-      for (int m = 0; m < DM_NMIX; ++m) {
-        float v = l[m];
-        if (mode == 2) {
-          const uint32_t rr = m < 4 ? r[m] : (m < 8 ? r2[m - 4] : r3[m - 8]);
-          const float u = 1e-5f + (1.f - 2e-5f) * Philox::u01(rr);
-          v -= logf(-logf(u));
-        }
-        if (v > best) { best = v; am = m; }
-      }
-#pragma unroll
-      for (int m = 0; m < DM_NMIX; ++m) sel[m] = (m == am) ? 1.f : 0.f;
-    }
-    float mu[3], ls[3], co[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float a = 0.f, s = 0.f, k = 0.f;
-#pragma unroll
-      for (int m = 0; m < DM_NMIX; ++m) {
-        a += l[10 + 30 * c + m] * sel[m];
-        s += l[10 + 30 * c + 10 + m] * sel[m];
-        k += tanhf(l[10 + 30 * c + 20 + m]) * sel[m];
-      }
-      mu[c] = a; ls[c] = fmaxf(s, DM_MIN_LS); co[c] = k;
-    }
+    DmDec d;
+    DmWords wd;
     if (mode == 2) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        ls[c] += logt;
-        const float u = 1e-5f + (1.f - 2e-5f) * Philox::u01(c == 0 ? r3[2] : (c == 1 ? r3[3] : r2[3] ^ 0x9E3779B9u));
-        mu[c] += expf(ls[c]) * (logf(u) - logf(1.f - u));
-      }
+      dm_words(seed, off, stream_id, gi, wd);
+      dm_decode_px<true>(l, mode, wd, logt, d, xs, sc);
+    } else {
+      dm_decode_px<false>(l, mode, wd, 0.f, d, xs, sc);
     }
-    const float x0 = fminf(fmaxf(mu[0], -1.f), 1.f);
-    const float x1 = fminf(fmaxf(mu[1] + co[0] * x0, -1.f), 1.f);
-    const float x2 = fminf(fmaxf(mu[2] + co[1] * x0 + co[2] * x1, -1.f), 1.f);
-    const float xs[3] = {x0, x1, x2};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int64_t o = ((int64_t)b * 3 + c) * npix + px;
       xo[o] = xs[c];
-      so[o] = expf(ls[c]);
+      so[o] = sc[c];
     }
+  }
+}
+
+// Backward of dmol_decode_kernel, same modes; mode 2 replays the forward's Philox words from the same rng pair / stream_id.
+// g_x, g_scale (nullable): NCHW f32, both multiplied by gscale.  Overwrites all 100 logit gradients of every pixel.
+template <typename T>
+__global__ __launch_bounds__(256) void dmol_decode_bwd_kernel(int n, int h, int w, View logits, int mode, const uint64_t* rng,
+                                                              uint32_t stream_id, float logt, const float* g_x, const float* g_scale,
+                                                              float gscale, View g_logits) {
+  const int npix = h * w;
+  const int64_t total = (int64_t)n * npix;
+  uint64_t seed = 0, off = 0;
+  if (mode == 2) { seed = rng[0]; off = rng[1]; }
+  for (int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x; gi < total; gi += (int64_t)gridDim.x * 256) {
+    const int b = (int)(gi / npix), px = (int)(gi % npix), py = px / w, pxx = px % w;
+    float l[100], xs[3], sc[3], gx[3], gsc[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int64_t o = ((int64_t)b * 3 + c) * npix + px;
+      gx[c] = g_x[o] * gscale;
+      gsc[c] = g_scale ? g_scale[o] * gscale : 0.f;
+    }
+    dm_load<T>(vptr<T>(logits, b, py, pxx), l);
+    DmDec d;
+    DmWords wd;
+    T* go = vptr<T>(g_logits, b, py, pxx);
+    if (mode == 2) {
+      dm_words(seed, off, stream_id, gi, wd);
+      dm_decode_px<true>(l, mode, wd, logt, d, xs, sc);
+      dm_decode_bwd_px<T, true>(l, mode, d, logt, gx, gsc, go);
+    } else {
+      dm_decode_px<false>(l, mode, wd, 0.f, d, xs, sc);
+      dm_decode_bwd_px<T, false>(l, mode, d, 0.f, gx, gsc, go);
+    }
+  }
+}
+
+// The counterfactual pixel step over two DmolNet mean decodes (mode 0 / 1 / 10 + k), as cf_dgauss_bwd_kernel is over
+// DGaussNet: (rec_loc, rec_scale), (cf_loc, cf_scale) = decode(rec / cf logits); cf_x = clamp(cf_loc + cf_scale *
+// (x - rec_loc) / max(rec_scale, 1e-12), -1, 1).  Given d loss / d cf_x (NCHW f32, times gscale) it writes both 100-channel
+// logit gradients.  One set of 100 logits is live at a time: rec is decoded first and only its DmDec is kept, cf is decoded
+// and back-propagated with its logits live, then rec's logits are reloaded for its own backward.
+template <typename T>
+__global__ __launch_bounds__(256) void cf_dmol_bwd_kernel(int n, int h, int w, int mode, View rec, View cf, View x, const float* g_cfx,
+                                                          float gscale, View g_rec, View g_cf) {
+  const int npix = h * w;
+  const int64_t total = (int64_t)n * npix;
+  const DmWords wd = {};
+  for (int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x; gi < total; gi += (int64_t)gridDim.x * 256) {
+    const int b = (int)(gi / npix), px = (int)(gi % npix), py = px / w, pxx = px % w;
+    float l[100], rloc[3], rsc[3], cloc[3], csc[3];
+    DmDec rd, cd;
+    dm_load<T>(vptr<T>(rec, b, py, pxx), l);
+    dm_decode_px<false>(l, mode, wd, 0.f, rd, rloc, rsc);
+    dm_load<T>(vptr<T>(cf, b, py, pxx), l);
+    dm_decode_px<false>(l, mode, wd, 0.f, cd, cloc, csc);
+    const T* xp = vptr<T>(x, b, py, pxx);
+    float g_rloc[3], g_rsc[3], g_cloc[3], g_csc[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float rs = fmaxf(rsc[c], 1e-12f);
+      const float u = (Elem<T>::ld(xp + c) - rloc[c]) / rs;
+      const float y = cloc[c] + csc[c] * u;
+      const float gy = (y >= -1.f && y <= 1.f) ? g_cfx[((int64_t)b * 3 + c) * npix + px] * gscale : 0.f;
+      g_cloc[c] = gy;
+      g_csc[c] = gy * u;
+      const float gu = gy * csc[c];
+      g_rloc[c] = -gu / rs;
+      g_rsc[c] = rsc[c] >= 1e-12f ? -gu * u / rs : 0.f;
+    }
+    dm_decode_bwd_px<T, false>(l, mode, cd, 0.f, g_cloc, g_csc, vptr<T>(g_cf, b, py, pxx));
+    dm_load<T>(vptr<T>(rec, b, py, pxx), l);
+    dm_decode_bwd_px<T, false>(l, mode, rd, 0.f, g_rloc, g_rsc, vptr<T>(g_rec, b, py, pxx));
   }
 }
 
@@ -754,6 +910,37 @@ extern "C" int cgen_dmol_decode(int32_t dtype, int32_t n, int32_t h, int32_t w, 
   if (dtype == CGEN_F32) hipLaunchKernelGGL(dmol_decode_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, h, w, mk(logits), mode, rng, stream_id, logt, x_nchw, scale_nchw);
   else hipLaunchKernelGGL(dmol_decode_kernel<h16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, h, w, mk(logits), mode, rng, stream_id, logt, x_nchw, scale_nchw);
   return check_launch("cgen_dmol_decode");
+}
+
+extern "C" int cgen_dmol_decode_bwd(int32_t dtype, int32_t n, int32_t h, int32_t w, cgen_view logits, int32_t mode,
+                                    const uint64_t* rng, uint32_t stream_id, float logt, const float* g_x_nchw,
+                                    const float* g_scale_nchw, float gscale, cgen_view g_logits, cgen_stream_t stream) {
+  CGEN_REQUIRE(dtype == CGEN_F32 || dtype == CGEN_F16, "cgen_dmol_decode_bwd: bad dtype %d", dtype);
+  CGEN_REQUIRE(logits.c == 100 && g_logits.c == 100, "cgen_dmol_decode_bwd: logits and g_logits need 100 channels, got %d and %d",
+               logits.c, g_logits.c);
+  CGEN_REQUIRE((mode >= 0 && mode <= 2) || (mode >= 11 && mode <= 19), "cgen_dmol_decode_bwd: bad mode %d", mode);
+  CGEN_REQUIRE(mode != 2 || rng, "cgen_dmol_decode_bwd: mode 2 needs the forward's rng pair");
+  CGEN_REQUIRE(n >= 0 && h > 0 && w > 0 && logits.p && g_x_nchw && g_logits.p, "cgen_dmol_decode_bwd: bad args");
+  const int grid = like_grid((int64_t)n * h * w);
+  if (dtype == CGEN_F32) hipLaunchKernelGGL(dmol_decode_bwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, h, w, mk(logits), mode, rng, stream_id, logt, g_x_nchw, g_scale_nchw, gscale, mk(g_logits));
+  else hipLaunchKernelGGL(dmol_decode_bwd_kernel<h16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, h, w, mk(logits), mode, rng, stream_id, logt, g_x_nchw, g_scale_nchw, gscale, mk(g_logits));
+  return check_launch("cgen_dmol_decode_bwd");
+}
+
+extern "C" int cgen_cf_dmol_bwd(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t mode, cgen_view rec_logits,
+                                cgen_view cf_logits, cgen_view x, const float* g_cfx_nchw, float gscale,
+                                cgen_view g_rec_logits, cgen_view g_cf_logits, cgen_stream_t stream) {
+  CGEN_REQUIRE(dtype == CGEN_F32 || dtype == CGEN_F16, "cgen_cf_dmol_bwd: bad dtype %d", dtype);
+  CGEN_REQUIRE(rec_logits.c == 100 && cf_logits.c == 100 && g_rec_logits.c == 100 && g_cf_logits.c == 100,
+               "cgen_cf_dmol_bwd: logits and their gradients need 100 channels");
+  CGEN_REQUIRE(mode == 0 || mode == 1 || (mode >= 11 && mode <= 19), "cgen_cf_dmol_bwd: bad mode %d (a mean: 0, 1 or 10 + k)", mode);
+  CGEN_REQUIRE(n >= 0 && h > 0 && w > 0 && rec_logits.p && cf_logits.p && x.p && x.c == 3 && g_cfx_nchw && g_rec_logits.p &&
+                   g_cf_logits.p,
+               "cgen_cf_dmol_bwd: bad args");
+  const int grid = like_grid((int64_t)n * h * w);
+  if (dtype == CGEN_F32) hipLaunchKernelGGL(cf_dmol_bwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, h, w, mode, mk(rec_logits), mk(cf_logits), mk(x), g_cfx_nchw, gscale, mk(g_rec_logits), mk(g_cf_logits));
+  else hipLaunchKernelGGL(cf_dmol_bwd_kernel<h16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, h, w, mode, mk(rec_logits), mk(cf_logits), mk(x), g_cfx_nchw, gscale, mk(g_rec_logits), mk(g_cf_logits));
+  return check_launch("cgen_cf_dmol_bwd");
 }
 
 extern "C" int cgen_elbo_finalize(int32_t n, const float* nll_part, int32_t nll_count, float nll_div, const float* kl_part,

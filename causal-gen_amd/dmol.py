@@ -3,15 +3,17 @@
 Module-level functions, import-compatible with the reference (channels-LAST tensors, 10 mixtures x RGB):
 
     discretized_mix_logistic_loss(x, l)                         dmol.py:24-118   -> [B] nats/dim, differentiable w.r.t. ``l``
-    sample_from_discretized_mix_logistic(l, nr_mix, ...)        dmol.py:121-161
-    mean_discretized_mix_logistic(l, nr_mix, mask, ...)         dmol.py:164-215
+    sample_from_discretized_mix_logistic(l, nr_mix, ...)        dmol.py:121-161  -> differentiable w.r.t. ``l``
+    mean_discretized_mix_logistic(l, nr_mix, mask, ...)         dmol.py:164-215  -> differentiable w.r.t. ``l``
 
 and ``DmolNet`` with ``forward / nll / sample`` (dmol.py:218-245), swapped into ``HVAE.likelihood`` exactly as in the
 reference (SURVEY probe C.6): ``m.likelihood = DmolNet(args)``.  The 1x1 conv (w0 -> 100 logits) runs through the MFMA conv
-kernel; the log-prob / mean / sample math is the fused kernels ``cgen_dmol_nll_fwd/bwd`` and ``cgen_dmol_decode``
-(``mask`` in {"soft", "hard", "top<k>"}).  HIP only: there is no ATen / CPU fallback (CPU tensors raise ``CgenError``).
-Inside an HVAE the model's engine drives the same kernels on its own tape; the standalone entry points below run on a
-private engine (``DmolNet``) or straight on the caller's tensors (module-level functions).
+kernel; the log-prob / mean / sample math is the fused kernels ``cgen_dmol_nll_fwd/bwd`` and ``cgen_dmol_decode`` /
+``cgen_dmol_decode_bwd`` (``mask`` in {"soft", "hard", "top<k>"}).  HIP only: there is no ATen / CPU fallback (CPU tensors
+raise ``CgenError``).  Inside an HVAE the model's engine drives the same kernels on its own tape (``DSCM.forward`` under
+autograd back-propagates the counterfactual pixels through ``cgen_cf_dmol_bwd``); the standalone entry points below run on a
+private engine (``DmolNet``, inference only) or straight on the caller's tensors (module-level functions, with gradients when
+``l.requires_grad``).
 """
 import torch
 from torch import nn
@@ -75,8 +77,8 @@ def discretized_mix_logistic_loss(x, l, low_bit=False):
 _FREE_RNG = {}
 
 
-def _decode(name, l, nr_mix, mode, logt, return_scale):
-    lib, lc = _prep(name, l, nr_mix)
+def _decode_launch(lib, lc, mode, logt):
+    """One `cgen_dmol_decode` launch on prepared logits -> (x, scale) channels last, and the rng pair it read (mode 2)."""
     B, H, W, _ = lc.shape
     dev = lc.device
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -90,7 +92,46 @@ def _decode(name, l, nr_mix, mode, logt, return_scale):
         lib.rng_advance(rng.data_ptr(), 1, st)
     lib.dmol_decode(_lib.F32, B, H, W, _cl_view(lc, 100), mode, rng.data_ptr() if rng is not None else None, 977, float(logt),
                     xo.data_ptr(), so.data_ptr(), st)
-    x, s = xo.permute(0, 2, 3, 1), so.permute(0, 2, 3, 1)  # channels last, as the reference returns them
+    return xo.permute(0, 2, 3, 1), so.permute(0, 2, 3, 1), rng  # channels last, as the reference returns them
+
+
+class _DmolDecode(torch.autograd.Function):
+    """Mean / sample of the mixture as one differentiable node: the forward is the `cgen_dmol_decode` launch of the
+    no-grad path, the backward `cgen_dmol_decode_bwd` (the sample replays the forward's draws from a copy of its rng pair)."""
+
+    @staticmethod
+    def forward(ctx, l, name, nr_mix, mode, logt):
+        lib, lc = _prep(name, l, nr_mix)
+        x, s, rng = _decode_launch(lib, lc, mode, logt)
+        ctx.save_for_backward(lc, rng.clone() if rng is not None else None)
+        ctx.mode, ctx.logt, ctx.in_dtype = mode, float(logt), l.dtype
+        ctx.set_materialize_grads(False)
+        return x, s
+
+    @staticmethod
+    def backward(ctx, gx, gs):
+        lc, rng = ctx.saved_tensors
+        lib = _lib.load()
+        B, H, W, _ = lc.shape
+
+        def nchw(g):
+            return g.to(lc.device, torch.float32).permute(0, 3, 1, 2).contiguous()
+
+        gxn = nchw(gx) if gx is not None else torch.zeros((B, 3, H, W), dtype=torch.float32, device=lc.device)
+        gsn = nchw(gs) if gs is not None else None
+        gl = torch.empty_like(lc)
+        lib.dmol_decode_bwd(_lib.F32, B, H, W, _cl_view(lc, 100), ctx.mode, rng.data_ptr() if rng is not None else None, 977,
+                            ctx.logt, gxn.data_ptr(), gsn.data_ptr() if gsn is not None else None, 1.0, _cl_view(gl, 100),
+                            torch.cuda.current_stream(lc.device).cuda_stream)
+        return gl.to(ctx.in_dtype), None, None, None, None
+
+
+def _decode(name, l, nr_mix, mode, logt, return_scale):
+    if torch.is_grad_enabled() and isinstance(l, torch.Tensor) and l.requires_grad:
+        x, s = _DmolDecode.apply(l, name, nr_mix, mode, logt)
+    else:
+        lib, lc = _prep(name, l, nr_mix)
+        x, s, _ = _decode_launch(lib, lc, mode, logt)
     return (x, s) if return_scale else x
 
 
@@ -108,13 +149,15 @@ def _mask_mode(mask):
 
 def sample_from_discretized_mix_logistic(l, nr_mix, return_scale=False, t=None):
     """dmol.py:121-161: Gumbel-max over the mixture logits, one logistic draw per channel (temperature ``t`` on the scale),
-    sequential RGB clamp.  Noise: device Philox seeded from torch.initial_seed(); every call advances the counter."""
+    sequential RGB clamp.  Noise: device Philox seeded from torch.initial_seed(); every call advances the counter.
+    Differentiable w.r.t. ``l`` (the drawn mixture is a constant, the backward replays the same draws)."""
     logt = 0.0 if t is None else float(torch.as_tensor(t, dtype=torch.float32).log())
     return _decode("sample_from_discretized_mix_logistic", l, nr_mix, 2, logt, return_scale)
 
 
 def mean_discretized_mix_logistic(l, nr_mix, mask="soft", return_scale=False):
-    """dmol.py:164-215: mixture mean under a soft / hard / top-k mask, no sampling in observation space."""
+    """dmol.py:164-215: mixture mean under a soft / hard / top-k mask, no sampling in observation space.  Differentiable
+    w.r.t. ``l`` (the hard selection is a constant)."""
     return _decode("mean_discretized_mix_logistic", l, nr_mix, _mask_mode(mask), 0.0, return_scale)
 
 

@@ -926,12 +926,11 @@ class HVAE(nn.Module):
         Returns (out3 = [elbo, nll, kl], mean cf_x [B,C,R,R], var cf_x or None)."""
         from .dscm import cf_pixels
 
-        if self.likelihood.kind != "dgauss" or getattr(self.likelihood, "logit_space", False):
+        if self.likelihood.kind not in ("dgauss", "dmol") or getattr(self.likelihood, "logit_space", False):
             raise NotImplementedError(
-                "DSCM.forward under autograd (dscm.py:40-72 as train_cf.py:159-183 uses it) is built for the DGaussNet head: with DmolNet "
-                "the counterfactual pixels are the soft mixture mean of dmol.py:218-245, whose gradient w.r.t. the 100 logits per pixel "
-                "has no HIP kernel (cgen_dmol_decode is forward only).  The reference never fine-tunes a DMoL HVAE (config 3 is the "
-                "survey's construct); call DSCM.forward under torch.no_grad() with this head")
+                "DSCM.forward under autograd (dscm.py:40-72 as train_cf.py:159-183 uses it) is built for the DGaussNet and DmolNet "
+                "heads; the logit-space Gaussian head (simple_vae's GaussNet) has no differentiable counterfactual step: call "
+                "DSCM.forward under torch.no_grad() with it")
         eng = self.engine()
         eng.begin()
         eng.recording = True
@@ -967,11 +966,16 @@ class HVAE(nn.Module):
         return out3, cf_x, None
 
     def _decode_params(self, eng, params):
-        """DGaussNet.sample(h) with return_loc=True on ready-made head outputs -> (loc, scale) as NCHW f32."""
+        """The head's sample(h) with return_loc=True on ready-made head outputs -> (loc, scale) as NCHW f32: DGaussNet
+        (vae.py:413-422) or DmolNet's mixture mean under its mask (dmol.py:234-245)."""
         B, R, Cx = params.n, params.h, self.input_channels
         xo = torch.empty((B, Cx, R, R), dtype=torch.float32, device=eng.device)
         so = torch.empty_like(xo)
-        eng.lib.dgauss_sample(eng.dt, B, R, R, Cx, params.cv(), 0.0, None, 978, xo.data_ptr(), so.data_ptr(), eng.stream)
+        if self.likelihood.kind == "dgauss":
+            eng.lib.dgauss_sample(eng.dt, B, R, R, Cx, params.cv(), 0.0, None, 978, xo.data_ptr(), so.data_ptr(), eng.stream)
+        else:
+            eng.lib.dmol_decode(eng.dt, B, R, R, params.cv(), self._dmol_mode(True), None, 977, 0.0, xo.data_ptr(), so.data_ptr(),
+                                eng.stream)
         eng.launches += 1
         return xo, so
 
@@ -985,8 +989,12 @@ class HVAE(nn.Module):
             S = eng.set_loss_scale(B * float(Cx * R * R))  # (the same value _run_backward sets for this pass)
             for rec_params, cf_params in passes:
                 g_rec, g_cfp = eng.seed_grad(rec_params), eng.seed_grad(cf_params)
-                eng.lib.cf_dgauss_bwd(eng.dt, B, R, R, Cx, rec_params.cv(), cf_params.cv(), xin.cv(), g.data_ptr(), S / len(passes),
-                                      g_rec.cv(), g_cfp.cv(), eng.stream)
+                if self.likelihood.kind == "dgauss":
+                    eng.lib.cf_dgauss_bwd(eng.dt, B, R, R, Cx, rec_params.cv(), cf_params.cv(), xin.cv(), g.data_ptr(), S / len(passes),
+                                          g_rec.cv(), g_cfp.cv(), eng.stream)
+                else:
+                    eng.lib.cf_dmol_bwd(eng.dt, B, R, R, self._dmol_mode(True), rec_params.cv(), cf_params.cv(), xin.cv(), g.data_ptr(),
+                                        S / len(passes), g_rec.cv(), g_cfp.cv(), eng.stream)
                 eng.launches += 1
             self.__dict__["_coef_keep"] = g
         self._run_backward(g_elbo, g_nll, g_kl, beta)
@@ -1075,18 +1083,22 @@ class HVAE(nn.Module):
             eng.lib.dgauss_sample(eng.dt, B, R, R, Cx, params.cv(), 0.0, None if return_loc else eng.rng_ptr(), 978,
                                   xo.data_ptr(), so.data_ptr(), eng.stream)
         else:
-            if not return_loc:
-                mode = 2
-            elif "top" in lk.mask:  # dmol.py:178-180: "top3" -> int(mask[-1]), must be < 10
-                mode = 10 + int(lk.mask[-1])
-                assert 1 <= mode - 10 < 10, "invalid top_k"
-            else:
-                mode = {"soft": 0, "hard": 1}[lk.mask]
             logt = 0.0 if t is None else float(torch.tensor(t).log())
-            eng.lib.dmol_decode(eng.dt, B, R, R, params.cv(), mode, eng.rng_ptr(), 977, logt, xo.data_ptr(), so.data_ptr(),
-                                eng.stream)
+            eng.lib.dmol_decode(eng.dt, B, R, R, params.cv(), self._dmol_mode(return_loc), eng.rng_ptr(), 977, logt, xo.data_ptr(),
+                                so.data_ptr(), eng.stream)
         eng.launches += 1
         return xo, so
+
+    def _dmol_mode(self, return_loc):
+        """cgen_dmol_decode's mode for DmolNet.sample(h, return_loc): 2 draws a sample, else the mean under likelihood.mask."""
+        if not return_loc:
+            return 2
+        mask = self.likelihood.mask
+        if "top" in mask:  # dmol.py:178-180: "top3" -> int(mask[-1]), must be < 10
+            mode = 10 + int(mask[-1])
+            assert 1 <= mode - 10 < 10, "invalid top_k"
+            return mode
+        return {"soft": 0, "hard": 1}[mask]
 
     def _begin_inference(self):
         eng = self.engine()

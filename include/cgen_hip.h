@@ -58,7 +58,7 @@ typedef struct cgen_view {
 /* ABI version of this header.  cgen_version() of the loaded library must equal it (causal-gen_amd/_lib.py checks): struct layouts,
  * enum values and signatures are only compatible within one version.  cgen_h16_format(): the 16-bit storage format the library was
  * BUILT for -- 0 = IEEE binary16 (default), 1 = bfloat16 (-DCGEN_H16_BF16, an A/B build); CGEN_F16 tensors must be in that format. */
-#define CGEN_ABI_VERSION 407
+#define CGEN_ABI_VERSION 408
 int cgen_version(void);
 int cgen_h16_format(void);
 const char* cgen_last_error(void);
@@ -407,6 +407,13 @@ int cgen_dmol_nll_bwd(int32_t dtype, int32_t n, int32_t h, int32_t w, cgen_view 
  * 10 + k (k = 1..9): top-k mean -- mixtures below the k-th largest logit are switched off and the rest renormalised */
 int cgen_dmol_decode(int32_t dtype, int32_t n, int32_t h, int32_t w, cgen_view logits, int32_t mode,
                      const uint64_t* rng, uint32_t stream_id, float logt, float* x_nchw, float* scale_nchw, cgen_stream_t);
+/* Backward of cgen_dmol_decode (same mode numbering; mode 2 replays the forward's rng pair / stream_id / logt, so the caller
+ * keeps a copy of the pair the forward launch read): g_x_nchw, g_scale_nchw (nullable) are the f32 NCHW gradients of x and
+ * scale; writes all 100 channels of g_logits (zeros included), scaled by gscale.  The hard mean and the sample treat the
+ * selected mixture as a constant; the soft and top-k means back-propagate through the softmax over the kept mixtures. */
+int cgen_dmol_decode_bwd(int32_t dtype, int32_t n, int32_t h, int32_t w, cgen_view logits, int32_t mode,
+                         const uint64_t* rng, uint32_t stream_id, float logt, const float* g_x_nchw,
+                         const float* g_scale_nchw, float gscale, cgen_view g_logits, cgen_stream_t);
 /* elbo/nll/kl (vae.py:450-457): nll = mean_b( sum(nll_part[b]) / nll_div ), kl = mean_b( sum(kl_part[b]) / kl_div ),
  * out3 = {nll + beta*kl, nll, kl}.  kl_part: [nkl][B] per-sample sums already reduced per layer by the caller's
  * layout: kl_part[b*kl_stride + j], j < kl_count.  beta_dev (optional, device memory) overrides beta, so a captured
@@ -425,6 +432,11 @@ int cgen_elbo_finalize_fb(int32_t n, const float* nll_part, int32_t nll_count, f
 int cgen_cf_dgauss_bwd(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, cgen_view rec_params, cgen_view cf_params,
                        cgen_view x, const float* g_cfx_nchw, float gscale, cgen_view g_rec_params, cgen_view g_cf_params,
                        cgen_stream_t);
+/* The same over two DmolNet mean decodes (dmol.py:234-245 with return_loc=True; mode 0 / 1 / 10 + k as in cgen_dmol_decode):
+ * one launch per particle writes both 100-channel logit gradients (NHWC, same layout as the logits). */
+int cgen_cf_dmol_bwd(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t mode, cgen_view rec_logits,
+                     cgen_view cf_logits, cgen_view x, const float* g_cfx_nchw, float gscale,
+                     cgen_view g_rec_logits, cgen_view g_cf_logits, cgen_stream_t);
 /* Counterfactual pixel step (dscm.py:55-63): u=(x-rec_loc)/max(rec_scale,1e-12); cf=clamp(cf_loc+cf_scale*u,-1,1);
  * optional running sums sum_x += cf, sum_x2 += cf^2.  All NCHW f32 contiguous, `count` elements. */
 int cgen_cf_pixels(int64_t count, const float* x, const float* rec_loc, const float* rec_scale, const float* cf_loc,
