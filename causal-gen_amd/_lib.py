@@ -71,6 +71,15 @@ class AdamwArgs(C.Structure):
                 ("state_dev", C.c_void_p)]
 
 
+class PredHead(C.Structure):
+    _fields_ = [("c", C.c_int32), ("res", C.c_int32), ("width", C.c_int32), ("nout", C.c_int32), ("ctx", C.c_int32),
+                ("kind", C.c_int32), ("tanh_loc", C.c_int32), ("obs_stride", C.c_int32), ("std_fixed", C.c_float),
+                ("reserved", C.c_int32), ("w", C.c_void_p * 8), ("b", C.c_void_p * 8), ("y", C.c_void_p), ("obs", C.c_void_p)]
+
+
+PRED_NORMAL, PRED_CATEGORICAL, PRED_BERNOULLI = 0, 1, 2
+PRED_MAX_HEADS, PRED_MAX_OUT = 4, 16
+
 i32, i64, u32, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p
 
 # name -> argtypes (all return int unless listed in _RESTYPES).  Kept in lock-step with include/cgen_hip.h;
@@ -145,13 +154,18 @@ PROTOTYPES = {
     "cgen_clip_decide": [vp, i32, vp, f32, f32, vp, vp],
     "cgen_adamw_ema": [C.POINTER(AdamwArgs), vp],
     "cgen_step_commit": [vp, vp],
+    "cgen_predictor_supported": [C.POINTER(PredHead), i32],
+    "cgen_predictor_workspace": [C.POINTER(PredHead), i32, C.POINTER(i64)],
+    "cgen_predictor_fwd": [C.POINTER(PredHead), i32, i32, vp, vp, vp, vp, vp, vp],
+    "cgen_predictor_bwd": [C.POINTER(PredHead), i32, i32, vp, vp, vp, vp, vp],
     "cgen_philox_normal": [vp, i64, vp, u32, vp],
     "cgen_rng_advance": [vp, u64, vp],
 }
 _RESTYPES = {"cgen_last_error": C.c_char_p}
-ABI_VERSION = 408  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
+ABI_VERSION = 409  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
 _NOCHECK = {"cgen_version", "cgen_h16_format", "cgen_last_error", "cgen_conv2d_wgrad_plan", "cgen_reparam_kl_chunks", "cgen_like_chunks",
-            "cgen_block3_supported", "cgen_block4_supported", "cgen_block4_pair_supported", "cgen_block3_pair_supported", "cgen_conv2d_pair_supported", "cgen_stem_conv_supported"}
+            "cgen_block3_supported", "cgen_block4_supported", "cgen_block4_pair_supported", "cgen_block3_pair_supported", "cgen_conv2d_pair_supported", "cgen_stem_conv_supported",
+            "cgen_predictor_supported"}
 
 
 class WgradBatchLaunch(C.Structure):

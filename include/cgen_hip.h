@@ -58,7 +58,7 @@ typedef struct cgen_view {
 /* ABI version of this header.  cgen_version() of the loaded library must equal it (causal-gen_amd/_lib.py checks): struct layouts,
  * enum values and signatures are only compatible within one version.  cgen_h16_format(): the 16-bit storage format the library was
  * BUILT for -- 0 = IEEE binary16 (default), 1 = bfloat16 (-DCGEN_H16_BF16, an A/B build); CGEN_F16 tensors must be in that format. */
-#define CGEN_ABI_VERSION 408
+#define CGEN_ABI_VERSION 409
 int cgen_version(void);
 int cgen_h16_format(void);
 const char* cgen_last_error(void);
@@ -441,6 +441,43 @@ int cgen_cf_dmol_bwd(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t mod
  * optional running sums sum_x += cf, sum_x2 += cf^2.  All NCHW f32 contiguous, `count` elements. */
 int cgen_cf_pixels(int64_t count, const float* x, const float* rec_loc, const float* rec_scale, const float* cf_loc,
                    const float* cf_scale, float* cf_x, float* sum_x, float* sum_x2, cgen_stream_t);
+
+/* ------------------------------------------------------------------ anticausal predictors (ABI 409)
+ * The reference's pgm/layers.py CNN in eval mode (conv7x7 -> [maxpool2] -> five 3x3 convs -> spatial mean -> [cat y] -> Linear ->
+ * Linear), every BatchNorm folded into the preceding conv / linear as weight scale + bias, followed by the per-variable negative
+ * log-likelihood of flow_pgm.py's model_anticausal (Normal with optional tanh on the loc, OneHotCategorical(probs=softmax),
+ * Bernoulli(probs=sigmoid); probabilities clamped to [eps, 1-eps] with eps = FLT_EPSILON as torch's clamp_probs does).
+ * One record per CNN head; all heads of one call read the same image x (NCHW f32 contiguous, [n, c, res, res]).
+ * Fused path (ws == NULL): one workgroup per image keeps the whole activation stack in LDS (cgen_predictor_supported says when).
+ * Workspace path (ws != NULL): the same kernel with the activation stack in ws, n * cgen_predictor_workspace() floats. */
+#define CGEN_PRED_MAX_HEADS 4
+#define CGEN_PRED_MAX_OUT 16
+enum cgen_pred_kind { CGEN_PRED_NORMAL = 0, CGEN_PRED_CATEGORICAL = 1, CGEN_PRED_BERNOULLI = 2 };
+typedef struct cgen_pred_head {
+  int32_t c, res, width, nout; /* in_shape = (c, res, res), CNN width, num_outputs */
+  int32_t ctx;                 /* context_dim: y is [n, ctx] row-major, concatenated after the spatial mean */
+  int32_t kind;                /* cgen_pred_kind; NORMAL needs nout == 2, BERNOULLI nout == 1, CATEGORICAL nout >= 2 */
+  int32_t tanh_loc;            /* NORMAL: loc = tanh(out[0]) */
+  int32_t obs_stride;          /* row stride (floats) of obs */
+  float std_fixed;             /* NORMAL: > 0 = constant scale, else softplus(out[1]) */
+  int32_t reserved;
+  const float* w[8];           /* folded weights: w[0..5] convs [co][ci][k][k]; w[6] fc0 [8w][8w+ctx]; w[7] fc3 [nout][8w] */
+  const float* b[8];           /* matching biases [co] */
+  const float* y;              /* context, NULL iff ctx == 0 */
+  const float* obs;            /* observed value: NORMAL / BERNOULLI 1 float, CATEGORICAL nout floats (one-hot; first max wins) */
+} cgen_pred_head;
+/* 1 if the fused (LDS) path takes these heads, 0 if not (and for invalid records: the launches say why) */
+int cgen_predictor_supported(const cgen_pred_head* heads, int32_t nheads);
+/* floats of workspace per image for the workspace path */
+int cgen_predictor_workspace(const cgen_pred_head* heads, int32_t nheads, int64_t* floats_per_image);
+/* Forward: terms[b*nheads + h] = -log p_h(obs_h[b] | x[b], y_h[b]); outs (optional) [nheads][n][CGEN_PRED_MAX_OUT] = the raw head
+ * outputs; loss (optional, f32[1]) = sum of all terms, reduced in a fixed order (bit-identical from run to run). */
+int cgen_predictor_fwd(const cgen_pred_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, float* terms, float* outs,
+                       float* loss, cgen_stream_t);
+/* Backward: dx = coef_dev[0] * d(sum of terms)/dx (overwritten, NCHW like x).  The heads' contributions are summed in a fixed
+ * order inside each image's workgroup; no atomics.  Recomputes the forward. */
+int cgen_predictor_bwd(const cgen_pred_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, const float* coef_dev,
+                       float* dx, cgen_stream_t);
 
 /* ------------------------------------------------------------------ step tail (K17; trainer.py:67-87, utils.py:178-225)
  * Flat-buffer fused global-norm -> clip -> skip predicate -> AdamW -> EMA.
