@@ -7,6 +7,7 @@
 namespace cgen {
 
 // state_dev: [0] sum_sq  [1] grad_norm  [2] clip_coef  [3] skip_flag  [4] n_skipped  [5] opt_steps (successful steps so far)
+//            [6] skips for a non-finite norm (of [4])
 
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* g, int64_t count, float* partial) {
   __shared__ float sm[4];
@@ -100,6 +101,8 @@ extern "C" int cgen_clip_decide(const float* partial, int32_t nblk, const float*
 
 extern "C" int cgen_adamw_ema(const cgen_adamw_args* a, cgen_stream_t stream) {
   CGEN_REQUIRE(a && a->p && a->g && a->m && a->v && a->state_dev && a->count >= 0, "cgen_adamw_ema: bad args");
+  // (LambdaLR(linear_warmup) divides by the warm-up length: 0 would make the first step's lr 0/0 and every weight NaN)
+  CGEN_REQUIRE(a->warmup_steps > 0, "cgen_adamw_ema: warmup_steps must be > 0 (got %d)", a->warmup_steps);
   if (a->count == 0) return CGEN_OK;
   AdamP p;
   p.p = a->p; p.g = a->g; p.m = a->m; p.v = a->v; p.ema = a->ema; p.count = a->count;

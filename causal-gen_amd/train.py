@@ -82,6 +82,8 @@ class TrainStep:
     NORM_BLOCKS = 1024
 
     def __init__(self, model, args, ema=True, use_graph=True, process_group=None, bucket_mb=32):
+        if int(args.lr_warmup_steps) <= 0:  # (before any device work) the kernel's LambdaLR(linear_warmup) divides by it
+            raise ValueError(f"lr_warmup_steps must be > 0 (got {args.lr_warmup_steps}): the linear warm-up divides by it")
         self.model, self.args = model, args
         self.lib = _lib.require_gpu()  # (the step tail's own kernels; the model's launches go through eng.lib, the staging proxy)
         self.use_graph = use_graph
