@@ -158,14 +158,18 @@ PROTOTYPES = {
     "cgen_predictor_workspace": [C.POINTER(PredHead), i32, C.POINTER(i64)],
     "cgen_predictor_fwd": [C.POINTER(PredHead), i32, i32, vp, vp, vp, vp, vp, vp],
     "cgen_predictor_bwd": [C.POINTER(PredHead), i32, i32, vp, vp, vp, vp, vp],
+    "cgen_predictor_tiled_supported": [C.POINTER(PredHead), i32],
+    "cgen_predictor_tiled_workspace": [C.POINTER(PredHead), i32, i32, C.POINTER(i64)],
+    "cgen_predictor_tiled_fwd": [C.POINTER(PredHead), i32, i32, vp, vp, i64, vp, vp, vp, vp],
+    "cgen_predictor_tiled_bwd": [C.POINTER(PredHead), i32, i32, vp, vp, i64, vp, vp, vp],
     "cgen_philox_normal": [vp, i64, vp, u32, vp],
     "cgen_rng_advance": [vp, u64, vp],
 }
 _RESTYPES = {"cgen_last_error": C.c_char_p}
-ABI_VERSION = 409  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
+ABI_VERSION = 410  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
 _NOCHECK = {"cgen_version", "cgen_h16_format", "cgen_last_error", "cgen_conv2d_wgrad_plan", "cgen_reparam_kl_chunks", "cgen_like_chunks",
             "cgen_block3_supported", "cgen_block4_supported", "cgen_block4_pair_supported", "cgen_block3_pair_supported", "cgen_conv2d_pair_supported", "cgen_stem_conv_supported",
-            "cgen_predictor_supported"}
+            "cgen_predictor_supported", "cgen_predictor_tiled_supported"}
 
 
 class WgradBatchLaunch(C.Structure):

@@ -4,8 +4,8 @@
 reference PGM checkpoint load with ``strict=True``.  The predictors are frozen and in eval mode during counterfactual
 fine-tuning (train_cf.py:123-124, dscm.py:23-24): every BatchNorm is a per-channel affine, folded once into the preceding conv /
 linear (refreshed when a parameter or buffer changes), and each PGM's image heads run in ONE HIP launch per direction
-(csrc/predictor.hip): the trunk, the spatial mean, the head MLP and the per-variable log-likelihood of flow_pgm.py's
-``model_anticausal``.  Only the input gradient exists: ``d aux / d cf_x`` is what flows on into the HVAE.
+(csrc/predictor.hip; one launch per LAYER on the tiled path that large images take, see ``_choose_path``): the trunk, the spatial
+mean, the head MLP and the per-variable log-likelihood of flow_pgm.py's ``model_anticausal``.  Only the input gradient exists: ``d aux / d cf_x`` is what flows on into the HVAE.
 
 ``model_anticausal(**obs)`` returns the summed negative log-likelihood (what pyro's ``Trace_ELBO.differentiable_loss`` of the
 anticausal model with the empty guide computes); ``AnticausalELBO`` hands it to ``DSCM.forward`` as ``elbo_fn``.
@@ -84,6 +84,11 @@ class CNN(nn.Module):
                 new.__dict__[k] = _copy.deepcopy(v, memo)
         return new
 
+    def path(self, x: Tensor) -> str:
+        """The placement a call with this image batch takes now: "fused", "workspace" or "tiled"."""
+        kind = _lib.PRED_BERNOULLI if self.num_outputs == 1 else _lib.PRED_CATEGORICAL
+        return _path_of([_Head(self, kind, False, None, None)], {"x": x}, 0.0)
+
     def forward(self, x: Tensor, y: Tensor = None) -> Tensor:
         kind = _lib.PRED_BERNOULLI if self.num_outputs == 1 else _lib.PRED_CATEGORICAL  # (outputs only: the kind sets no math)
         spec = _Head(self, kind, False, None, "y" if y is not None else None)
@@ -125,7 +130,7 @@ def _layered() -> bool:
     return os.environ.get("CGEN_PREDICTOR_LAYERED", "0") == "1"
 
 
-def _records(heads, obs, std_fixed, need_obs):
+def _records(heads, obs, std_fixed, need_obs, need_ctx=True):
     """ctypes head records + the tensors they point into (kept alive by the caller)."""
     x = obs["x"]
     B, C, R = x.shape[0], x.shape[1], x.shape[-1]
@@ -142,7 +147,7 @@ def _records(heads, obs, std_fixed, need_obs):
         r.kind, r.tanh_loc, r.std_fixed = hd.kind, int(hd.tanh_loc), float(std_fixed)
         for i, (w, b) in enumerate(wb):
             r.w[i], r.b[i] = w.data_ptr(), b.data_ptr()
-        if cnn.context_dim:
+        if cnn.context_dim and need_ctx:
             y = _col(obs[hd.ctx_var], B, dev)
             if y.shape[1] != cnn.context_dim:
                 raise ValueError(f"predictor head for {hd.var}: context {hd.ctx_var} has {y.shape[1]} columns, expected {cnn.context_dim}")
@@ -155,20 +160,72 @@ def _records(heads, obs, std_fixed, need_obs):
     return recs, keep
 
 
-def _workspace(heads_owner, recs, n, dev):
-    """None for the fused (LDS) path, else a global activation workspace of n images (cached on the owner)."""
-    lib = _lib.require_gpu()
-    if not _layered() and lib._raw_cgen_predictor_supported(recs, len(recs)) == 1:
-        return None
-    per = _lib.i64(0)
-    lib.predictor_workspace(recs, len(recs), ctypes.byref(per))
-    need = per.value * n
-    ws = heads_owner.__dict__.get("_ws") if heads_owner is not None else None
+def _choose_path(lib, recs) -> str:
+    """Where a call runs: "fused" (activation stack in LDS, one workgroup per image), "workspace" (the same kernel with the stack
+    in global memory) or "tiled" (one launch per layer over tile x image x head).  CGEN_PREDICTOR_LAYERED=1 forces the workspace
+    path; else CGEN_PREDICTOR_TILED=1 takes the tiled path wherever it is supported and CGEN_PREDICTOR_TILED=0 never does; unset,
+    the fused path is taken where it fits, else the tiled one where supported, else the workspace."""
+    nh = len(recs)
+    if _layered():
+        return "workspace"
+    tiled = os.environ.get("CGEN_PREDICTOR_TILED")
+    tiled_ok = tiled != "0" and lib._raw_cgen_predictor_tiled_supported(recs, nh) == 1
+    if tiled == "1" and tiled_ok:
+        return "tiled"
+    if lib._raw_cgen_predictor_supported(recs, nh) == 1:
+        return "fused"
+    return "tiled" if tiled_ok else "workspace"
+
+
+def _cached(owner, key, need, dev):
+    ws = owner.__dict__.get(key) if owner is not None else None
     if ws is None or ws.numel() < need or ws.device != dev:
         ws = torch.empty(need, dtype=torch.float32, device=dev)
-        if heads_owner is not None:
-            heads_owner.__dict__["_ws"] = ws
+        if owner is not None:
+            owner.__dict__[key] = ws
     return ws
+
+
+def _route(heads_owner, recs, n, dev):
+    """(path, workspace or None) of a call; the workspaces are cached on the owner (one per placement).  A backward uses the
+    pair its forward got, whatever the environment says by then."""
+    lib = _lib.require_gpu()
+    path = _choose_path(lib, recs)
+    if path == "fused":
+        return path, None
+    need = _lib.i64(0)
+    if path == "tiled":
+        lib.predictor_tiled_workspace(recs, len(recs), n, ctypes.byref(need))
+        return path, _cached(heads_owner, "_ws_tiled", need.value, dev)
+    lib.predictor_workspace(recs, len(recs), ctypes.byref(need))
+    return path, _cached(heads_owner, "_ws", need.value * n, dev)
+
+
+def _fwd(lib, route, recs, n, x, terms, outs, loss):
+    path, ws = route
+    t, o, l = (v.data_ptr() if v is not None else None for v in (terms, outs, loss))
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    if path == "tiled":
+        lib.predictor_tiled_fwd(recs, len(recs), n, x.data_ptr(), ws.data_ptr(), ws.numel(), t, o, l, stream)
+    else:
+        lib.predictor_fwd(recs, len(recs), n, x.data_ptr(), ws.data_ptr() if ws is not None else None, t, o, l, stream)
+
+
+def _bwd(lib, route, recs, n, x, coef, dx):
+    path, ws = route
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    if path == "tiled":
+        lib.predictor_tiled_bwd(recs, len(recs), n, x.data_ptr(), ws.data_ptr(), ws.numel(), coef.data_ptr(), dx.data_ptr(), stream)
+    else:
+        lib.predictor_bwd(recs, len(recs), n, x.data_ptr(), ws.data_ptr() if ws is not None else None, coef.data_ptr(), dx.data_ptr(),
+                          stream)
+
+
+def _path_of(heads, obs, std_fixed) -> str:
+    lib = _lib.require_gpu()
+    x = _prep_x(obs["x"])
+    recs, keep = _records(heads, dict(obs, x=x), std_fixed, need_obs=False, need_ctx=False)
+    return _choose_path(lib, recs)
 
 
 def _prep_x(x: Tensor) -> Tensor:
@@ -184,10 +241,9 @@ def _run_outputs(heads, obs, std_fixed, owner=None):
     obs = dict(obs, x=x)
     B = x.shape[0]
     recs, keep = _records(heads, obs, std_fixed, need_obs=False)
-    ws = _workspace(owner, recs, B, x.device)
+    route = _route(owner, recs, B, x.device)
     outs = torch.empty(len(heads), B, _lib.PRED_MAX_OUT, device=x.device)
-    lib.predictor_fwd(recs, len(heads), B, x.data_ptr(), ws.data_ptr() if ws is not None else None, None, outs.data_ptr(), None,
-                      torch.cuda.current_stream(x.device).cuda_stream)
+    _fwd(lib, route, recs, B, x, None, outs, None)
     return [outs[h, :, :hd.cnn.num_outputs] for h, hd in enumerate(heads)]
 
 
@@ -201,22 +257,20 @@ class _PredictorNLL(torch.autograd.Function):
         B = xd.shape[0]
         full = dict(obs, x=xd)
         recs, keep = _records(heads, full, std_fixed, need_obs=True)
-        ws = _workspace(owner, recs, B, xd.device)
+        route = _route(owner, recs, B, xd.device)
         terms = torch.empty(B, len(heads), device=xd.device)
         loss = torch.empty(1, device=xd.device)
-        lib.predictor_fwd(recs, len(heads), B, xd.data_ptr(), ws.data_ptr() if ws is not None else None, terms.data_ptr(), None,
-                          loss.data_ptr(), torch.cuda.current_stream(xd.device).cuda_stream)
-        ctx.state = (recs, keep, xd, ws, x.device, x.dtype)
+        _fwd(lib, route, recs, B, xd, terms, None, loss)
+        ctx.state = (recs, keep, xd, route, x.device, x.dtype)
         return loss[0].to(x.device)
 
     @staticmethod
     def backward(ctx, g):
         lib = _lib.require_gpu()
-        recs, keep, xd, ws, xdev, xdt = ctx.state
+        recs, keep, xd, route, xdev, xdt = ctx.state
         coef = g.detach().reshape(1).float().to(xd.device).contiguous()
         dx = torch.empty_like(xd)
-        lib.predictor_bwd(recs, len(recs), xd.shape[0], xd.data_ptr(), ws.data_ptr() if ws is not None else None, coef.data_ptr(),
-                          dx.data_ptr(), torch.cuda.current_stream(xd.device).cuda_stream)
+        _bwd(lib, route, recs, xd.shape[0], xd, coef, dx)
         return dx.to(device=xdev, dtype=xdt), None, None, None, None
 
 
@@ -255,11 +309,14 @@ class _AnticausalPredictor(nn.Module):
         x = _prep_x(obs["x"])
         B = x.shape[0]
         recs, keep = _records(heads, dict(obs, x=x), self.std_fixed, need_obs=True)
-        ws = _workspace(self, recs, B, x.device)
+        route = _route(self, recs, B, x.device)
         terms = torch.empty(B, len(heads), device=x.device)
-        lib.predictor_fwd(recs, len(heads), B, x.data_ptr(), ws.data_ptr() if ws is not None else None, terms.data_ptr(), None, None,
-                          torch.cuda.current_stream(x.device).cuda_stream)
+        _fwd(lib, route, recs, B, x, terms, None, None)
         return {hd.var: terms[:, h] for h, hd in enumerate(heads)}
+
+    def path(self, x: Tensor) -> str:
+        """The placement a call with this image batch takes now: "fused", "workspace" or "tiled"."""
+        return _path_of(self._heads(), {"x": x}, self.std_fixed)
 
     def guide_pass(self, **obs) -> None:
         pass
@@ -283,7 +340,7 @@ class _AnticausalPredictor(nn.Module):
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k != "_ws":  # runtime workspace
+            if k not in ("_ws", "_ws_tiled"):  # runtime workspaces
                 new.__dict__[k] = _copy.deepcopy(v, memo)
         return new
 

@@ -58,7 +58,7 @@ typedef struct cgen_view {
 /* ABI version of this header.  cgen_version() of the loaded library must equal it (causal-gen_amd/_lib.py checks): struct layouts,
  * enum values and signatures are only compatible within one version.  cgen_h16_format(): the 16-bit storage format the library was
  * BUILT for -- 0 = IEEE binary16 (default), 1 = bfloat16 (-DCGEN_H16_BF16, an A/B build); CGEN_F16 tensors must be in that format. */
-#define CGEN_ABI_VERSION 409
+#define CGEN_ABI_VERSION 410
 int cgen_version(void);
 int cgen_h16_format(void);
 const char* cgen_last_error(void);
@@ -442,14 +442,17 @@ int cgen_cf_dmol_bwd(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t mod
 int cgen_cf_pixels(int64_t count, const float* x, const float* rec_loc, const float* rec_scale, const float* cf_loc,
                    const float* cf_scale, float* cf_x, float* sum_x, float* sum_x2, cgen_stream_t);
 
-/* ------------------------------------------------------------------ anticausal predictors (ABI 409)
+/* ------------------------------------------------------------------ anticausal predictors (ABI 409, tiled placement 410)
  * The reference's pgm/layers.py CNN in eval mode (conv7x7 -> [maxpool2] -> five 3x3 convs -> spatial mean -> [cat y] -> Linear ->
  * Linear), every BatchNorm folded into the preceding conv / linear as weight scale + bias, followed by the per-variable negative
  * log-likelihood of flow_pgm.py's model_anticausal (Normal with optional tanh on the loc, OneHotCategorical(probs=softmax),
  * Bernoulli(probs=sigmoid); probabilities clamped to [eps, 1-eps] with eps = FLT_EPSILON as torch's clamp_probs does).
  * One record per CNN head; all heads of one call read the same image x (NCHW f32 contiguous, [n, c, res, res]).
  * Fused path (ws == NULL): one workgroup per image keeps the whole activation stack in LDS (cgen_predictor_supported says when).
- * Workspace path (ws != NULL): the same kernel with the activation stack in ws, n * cgen_predictor_workspace() floats. */
+ * Workspace path (ws != NULL): the same kernel with the activation stack in ws, n * cgen_predictor_workspace() floats.
+ * Tiled path (cgen_predictor_tiled_*): one launch per layer whose grid covers (output tile x channel group x image x head), for
+ * images whose stack does not fit in LDS; the stacks of all heads of all images live in ws at the same time.  Same records,
+ * same terms / outs / loss / dx layouts and meanings as the other two. */
 #define CGEN_PRED_MAX_HEADS 4
 #define CGEN_PRED_MAX_OUT 16
 enum cgen_pred_kind { CGEN_PRED_NORMAL = 0, CGEN_PRED_CATEGORICAL = 1, CGEN_PRED_BERNOULLI = 2 };
@@ -478,6 +481,20 @@ int cgen_predictor_fwd(const cgen_pred_head* heads, int32_t nheads, int32_t n, c
  * order inside each image's workgroup; no atomics.  Recomputes the forward. */
 int cgen_predictor_bwd(const cgen_pred_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, const float* coef_dev,
                        float* dx, cgen_stream_t);
+/* 1 if the tiled path takes these heads: every shape the launches accept (c 1..4, res 8..512, width 8 / 16 / 24 / 32) with the
+ * SAME width in every head; 0 otherwise.  Never fails. */
+int cgen_predictor_tiled_supported(const cgen_pred_head* heads, int32_t nheads);
+/* floats of workspace for n images: n * nheads * (the floats of one head's activation stack, rounded up to a multiple of 4). */
+int cgen_predictor_tiled_workspace(const cgen_pred_head* heads, int32_t nheads, int32_t n, int64_t* floats);
+/* cgen_predictor_fwd / cgen_predictor_bwd on the tiled path.  ws must hold ws_floats >= cgen_predictor_tiled_workspace() floats; a
+ * null or too-small workspace and unequal head widths are rejected before anything is launched.  Every launch goes on `stream`,
+ * with no host synchronisation, allocation or read of device data (capturable).  dx is written by the stem's data-gradient
+ * launch, which adds the heads' contributions in head order inside one thread per element; reruns are bit-identical and image
+ * b's results do not depend on n or on b's position.  The backward recomputes the forward into ws. */
+int cgen_predictor_tiled_fwd(const cgen_pred_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, int64_t ws_floats,
+                             float* terms, float* outs, float* loss, cgen_stream_t);
+int cgen_predictor_tiled_bwd(const cgen_pred_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, int64_t ws_floats,
+                             const float* coef_dev, float* dx, cgen_stream_t);
 
 /* ------------------------------------------------------------------ step tail (K17; trainer.py:67-87, utils.py:178-225)
  * Flat-buffer fused global-norm -> clip -> skip predicate -> AdamW -> EMA.

@@ -1,6 +1,7 @@
 """Time the anticausal predictors: forward (loss) and forward + d/dx, HIP vs torch eager on the same GPU (the same eval-mode CNNs,
 torch.distributions, autograd.grad w.r.t. x).  Cases: morphomnist and cmnist at B = 256 (fused, and the workspace path forced
-with CGEN_PREDICTOR_LAYERED=1), ukbb192 at B = 32 (workspace path).  Prints one JSON line per case."""
+with CGEN_PREDICTOR_LAYERED=1; morphomnist also through the tiled path, for information), ukbb192 at B = 32 (workspace path and
+tiled path, the default there).  Prints one JSON line per case; each row times its own eager columns."""
 import json
 import os
 import sys
@@ -75,15 +76,18 @@ def eager_nll(pred, obs):
 
 
 def main():
-    cases = [("morphomnist", 1, 32, 256, "0"), ("morphomnist", 1, 32, 256, "1"), ("cmnist", 3, 32, 256, "0"), ("cmnist", 3, 32, 256, "1"),
-             ("ukbb192", 1, 192, 32, "1")]
-    for ds, C, R, B, layered in cases:
-        os.environ["CGEN_PREDICTOR_LAYERED"] = layered
+    cases = [("morphomnist", 1, 32, 256, "fused"), ("morphomnist", 1, 32, 256, "workspace"), ("morphomnist", 1, 32, 256, "tiled"),
+             ("cmnist", 3, 32, 256, "fused"), ("cmnist", 3, 32, 256, "workspace"), ("ukbb192", 1, 192, 32, "workspace"),
+             ("ukbb192", 1, 192, 32, "tiled")]
+    for ds, C, R, B, path in cases:
+        os.environ["CGEN_PREDICTOR_LAYERED"] = "1" if path == "workspace" else "0"
+        os.environ["CGEN_PREDICTOR_TILED"] = "1" if path == "tiled" else "0"
         g = torch.Generator().manual_seed(0)
         pred = P.make_predictor(SimpleNamespace(dataset=ds, input_channels=C, input_res=R, std_fixed=0.0))
         randomise(pred, g)
         pred = pred.cuda()
         obs = obs_for(ds, B, C, R, g)
+        assert pred.path(obs["x"]) == path, (pred.path(obs["x"]), path)
 
         def hip_fwd():
             with torch.no_grad():
@@ -101,7 +105,7 @@ def main():
             x = obs["x"].detach().requires_grad_(True)
             torch.autograd.grad(eager_nll(pred, dict(obs, x=x)), x)
 
-        row = {"case": ds, "B": B, "path": "workspace" if layered == "1" else "fused", "hip_fwd_ms": round(timeit(hip_fwd), 4),
+        row = {"case": ds, "B": B, "path": path, "hip_fwd_ms": round(timeit(hip_fwd), 4),
                "hip_fwd_bwd_ms": round(timeit(hip_fb), 4), "eager_fwd_ms": round(timeit(eager_fwd), 4),
                "eager_fwd_bwd_ms": round(timeit(eager_fb), 4)}
         print(json.dumps(row), flush=True)
