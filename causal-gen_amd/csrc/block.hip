@@ -109,7 +109,13 @@ __device__ __forceinline__ uint4 b3_pack8(const float* v) {
 }
 #define B3_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #define B3_VMWAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+// -DB3_DRAIN_WAITS (a debugging build): every hand-counted wait of this file becomes vmcnt(0).  Results must not change;
+// if they do, a count -- or what it assumes about the order of the requests -- is wrong.
+#ifdef B3_DRAIN_WAITS
+#define B3_VMWAIT_N(n) asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#else
 #define B3_VMWAIT_N(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+#endif
 // a 16-byte global load the compiler does NOT track (no automatic s_waitcnt in front of its uses): the caller waits by count
 // (B3_VMWAIT_N) and launders the register (b3_pin) before the first use.  The "memory" clobber keeps it in program order with the
 // LDS-DMA requests around it -- the counted waits depend on that order.  s_nop 4: the base may have been written by a VALU
@@ -117,12 +123,21 @@ __device__ __forceinline__ uint4 b3_pack8(const float* v) {
 // (VALU writes SGPR -> VMEM reads it: 5 wait states; without them the load uses the stale register: a memory fault).
 // one LDS-DMA instruction (16 B per lane -> LDS at `lds` + 16 lane), also invisible to the compiler's wait-count pass: no automatic
 // vmcnt(0) in front of LDS accesses it cannot prove disjoint, no limit on how many requests may be in flight; ordering is by the
-// counted waits + barriers of the tile loop alone.  (Nothing else in these kernels uses M0; s_nop: M0 write -> LDS-DMA hazard.)
+// counted waits + barriers of the tile loop alone.  (s_nop: M0 write -> LDS-DMA hazard.  M0 is written and read inside this ONE
+// statement and cannot be declared clobbered -- hipcc reserves it: "inline asm clobber list contains reserved registers", once per
+// inlined copy.  In the assembly of this file nothing reads M0 but a DMA instruction, and the only other writes are the
+// compiler's own, directly in front of the DMA builtin of the small-image instance, which does not come through here.)
 __device__ __forceinline__ void b3_dma16(const char* src, const uint32_t lds) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(lds) : "memory");
 }
 template <int N>
-__device__ __forceinline__ void b3_vmwait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
+__device__ __forceinline__ void b3_vmwait() {
+#ifdef B3_DRAIN_WAITS
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#else
+  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
+#endif
+}
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n in [LO, HI]: the count is an immediate, so a decision tree of them
 template <int LO, int HI>
 __device__ __forceinline__ void b3_vmwait_rt(const int n) {
@@ -944,7 +959,15 @@ __device__ __forceinline__ void blk3s_body(const B3P& p, const int bid, const in
     }
     for (int i = tid; i < ((R + 2) * B3S_MW * MS) >> 4; i += 64 * B3S_NW) *(uint4*)(MID + i * 16) = make_uint4(0, 0, 0, 0);
     B3S_STAMP(2);
-    B3_BARRIER();  // (the tables; hipcc drains vmcnt -- the DMA it tracks -- in front of the first read of the tile below)
+    // This wave's pieces of the input tile have landed BEFORE the barrier: after it every wave reads pieces that other waves
+    // requested, and only the requesting wave's own wait orders an LDS-DMA before a ds_read.  The compiler's drain is no substitute:
+    // it sits in front of the first LDS access of THIS wave that may alias the tile -- the zeroing loop above, which a wave with no
+    // part of the bottleneck tile to zero jumps over (12x12, 40 channels: 400 stores, wave 7 has none), or, in the data gradient,
+    // nowhere in front of the K loop at all.  That wave's pieces were then read by the others as whatever the slot held before:
+    // right almost always, stale bytes when a co-resident kernel slows the requests down (LABNOTES 12).  The fragments requested by
+    // KA.start are waited for here as well; seven of eight waves did that in the zeroing loop already.
+    B3_VMWAIT();
+    B3_BARRIER();  // (the tables, the zeros, everyone's pieces of the input tile)
     if constexpr (PRE) {  // ReLU once per element, in place (each is read by nine taps)
       for (int i = tid; i < ninst * 64; i += 64 * B3S_NW) {
         union { uint4 q; h16x8 h; } r;

@@ -1,7 +1,7 @@
 """Weight-gradient scheduling of the engine (a mixin of `Engine`): every weight gradient of a backward pass is a leaf, so they are
 deferred, planned once as horizontally batched launches (`cgen_conv2d_wgrad_batch_plan / _run`: one launch walks the record list
-of all pending problems), flushed at a mark of the backward chain with a capped grid -- in line on the main stream by default,
-on a side stream beside the chain with CGEN_WGRAD_BG_SERIAL=0 (LABNOTES 12) -- and their split-K
+of all pending problems), flushed at a mark of the backward chain -- in line on the main stream with the whole chip by default,
+on a side stream beside the chain with a capped grid with CGEN_WGRAD_BG_SERIAL=0 (LABNOTES 12) -- and their split-K
 partials reduced by multi-tensor launches (`cgen_wgrad_reduce`) in rounds with at most one event per conv site.  DESIGN.md 3.3.
 (reference: what `loss.backward()` does for the conv weights in trainer.py:64-67)"""
 import ctypes as C
@@ -165,10 +165,14 @@ class WgradMixin:
             for i in rest:
                 self.lib.conv2d_wgrad(C.byref(args[i]), self.stream)
                 self.launches += 1
-            # In line on the main stream by default: running beside the backward chain (CGEN_WGRAD_BG_SERIAL=0) the flushed batch
-            # now and then leaves a non-finite activation gradient in the encoder's chain (LABNOTES 12: only with cgen_block3 on), so
-            # the same arguments did not give the same training run twice
-            if os.environ.get("CGEN_WGRAD_BG_SERIAL", "1") != "0":
+            # In line on the main stream by default, without the grid cap: the cap only exists to leave the backward chain its share
+            # of the chip when the batch runs beside it (one wave writes each slab element whatever workgroup walks it: the cap
+            # never changes a result).  CGEN_WGRAD_BG_SERIAL=0 puts the batch on the side stream beside the chain, 0.7 ms per step
+            # faster.  (That form used to leave a non-finite encoder gradient in 3-10 of 2500 steps: the small-image fused Block
+            # kernel read input pieces one of its waves had not waited for; fixed in csrc/block.hip.  Why it is still not the
+            # default: LABNOTES 12.3.)
+            inline = os.environ.get("CGEN_WGRAD_BG_SERIAL", "1") != "0"
+            if inline:
                 side = main
             else:
                 side.wait_stream(main)
@@ -176,7 +180,7 @@ class WgradMixin:
                     side.wait_stream(self._fwd_side)
                 self._wg_forked = True
             if blob is not None and nl:
-                self.lib.conv2d_wgrad_batch_run(blob.data_ptr(), launches, nl, self.wgrad_bg_wgs, side.cuda_stream)
+                self.lib.conv2d_wgrad_batch_run(blob.data_ptr(), launches, nl, 0 if inline else self.wgrad_bg_wgs, side.cuda_stream)
                 self.launches += nl
             self._wg_deferred = []
             if self.wgrad_bg_reduce:
