@@ -3,3 +3,11 @@ the reference's own Python surface (``vae.HVAE``, ``dmol.DmolNet``, ``dscm.DSCM`
 gfx950 HIP kernels in ``libcgen_hip.so`` (C ABI: include/cgen_hip.h).  There is no CPU or ATen fallback: the
 model classes raise if the library or a GPU is missing."""
 __version__ = "0.1.0"
+
+
+def __getattr__(name):  # the data pipeline's classes, re-exported without importing torch at package import
+    if name in ("DeviceDataset", "DeviceLoader"):
+        import importlib
+
+        return getattr(importlib.import_module(__name__ + ".data"), name)
+    raise AttributeError(name)

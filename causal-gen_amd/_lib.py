@@ -77,6 +77,15 @@ class PredHead(C.Structure):
                 ("reserved", C.c_int32), ("w", C.c_void_p * 8), ("b", C.c_void_p * 8), ("y", C.c_void_p), ("obs", C.c_void_p)]
 
 
+class AugmentArgs(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("c", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32), ("r_h", C.c_int32),
+                ("r_w", C.c_int32), ("pad_x", C.c_int32), ("pad_y", C.c_int32), ("ctx", C.c_int32), ("stream_id", C.c_uint32),
+                ("hflip_p", C.c_float), ("sub", C.c_float), ("mul", C.c_float), ("n_data", C.c_int64), ("data", C.c_void_p),
+                ("index", C.c_void_p), ("out", View), ("rng", C.c_void_p), ("draws_in", C.c_void_p), ("draws_out", C.c_void_p),
+                ("pa_data", C.c_void_p), ("pa_out", C.c_void_p)]
+
+
+STREAM_AUGMENT = 980  # Philox stream id of cgen_batch_augment (the list of taken ids is in csrc/common.h)
 PRED_NORMAL, PRED_CATEGORICAL, PRED_BERNOULLI = 0, 1, 2
 PRED_MAX_HEADS, PRED_MAX_OUT = 4, 16
 
@@ -116,6 +125,8 @@ PROTOTYPES = {
     "cgen_axpby": [i32, i32, i32, i32, View, View, f32, f32, i32, i32, vp],
     "cgen_nchw_to_nhwc": [i32, i32, i32, i32, i32, i32, vp, View, f32, f32, vp],
     "cgen_nhwc_to_nchw": [i32, i32, i32, i32, i32, View, vp, vp],
+    "cgen_batch_augment": [C.POINTER(AugmentArgs), vp],
+    "cgen_batch_augment_arm": [C.POINTER(AugmentArgs)],
     "cgen_stem_conv_supported": [i32, i32, i32, i32],
     "cgen_stem_conv_fwd": [i32, i32, i32, i32, i32, i32, i32, View, vp, vp, View, vp],
     "cgen_im2col": [i32, i32, i32, i32, i32, View, View, vp],
@@ -166,10 +177,10 @@ PROTOTYPES = {
     "cgen_rng_advance": [vp, u64, vp],
 }
 _RESTYPES = {"cgen_last_error": C.c_char_p}
-ABI_VERSION = 410  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
+ABI_VERSION = 411  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
 _NOCHECK = {"cgen_version", "cgen_h16_format", "cgen_last_error", "cgen_conv2d_wgrad_plan", "cgen_reparam_kl_chunks", "cgen_like_chunks",
             "cgen_block3_supported", "cgen_block4_supported", "cgen_block4_pair_supported", "cgen_block3_pair_supported", "cgen_conv2d_pair_supported", "cgen_stem_conv_supported",
-            "cgen_predictor_supported", "cgen_predictor_tiled_supported"}
+            "cgen_predictor_supported", "cgen_predictor_tiled_supported", "cgen_batch_augment_arm"}
 
 
 class WgradBatchLaunch(C.Structure):

@@ -219,6 +219,13 @@ __device__ __forceinline__ float block_sum_256(float v, float* sm) {
 }
 
 // ----------------------------------------------------------------------------- Philox4x32-10 + Box-Muller
+// Stream ids of a (seed, offset) pair: two kernels of one pass must never share one.  Taken so far:
+//   0 .. n_blocks-1  the decoder's latent layers (reparam_kl / sample_gaussian; vae.py passes the block index)
+//   977              likelihood noise: DMoL decode / its backward, GaussNet's dequantisation uniforms
+//   978              DGaussNet.sample (vae.py)
+//   979              the config-1 model's samplers (simple_vae.py)
+//   980              cgen_batch_augment's crop / flip draws (keyed by data set row)
+#define CGEN_STREAM_AUGMENT 980u
 struct Philox {
   static __device__ __forceinline__ void round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
     const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;

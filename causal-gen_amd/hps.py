@@ -17,11 +17,12 @@ _DEFAULTS = dict(
     cond_prior=False, widths=[16, 32, 48, 64, 128], bottleneck=4, z_dim=16, z_max_res=192, bias_max_res=64,
     x_like="diag_dgauss", std_init=0.0, parents_x=["mri_seq", "brain_volume", "ventricle_volume", "sex"], concat_pa=False,
     context_dim=4, context_norm="log_standard", q_correction=False, dataset="",
+    pad=3, hflip=0.5,  # train-time augmentation (datasets.py; data.DeviceDataset.from_args maps them per data set)
 )
 _A192 = dict(enc_arch="192b1d2,96b3d2,48b7d2,24b11d2,12b7d2,6b3d6,1b2", dec_arch="1b2,6b4,12b8,24b12,48b8,96b4,192b2",
-             widths=[32, 64, 96, 128, 160, 192, 512], input_res=192, z_dim=16)
+             widths=[32, 64, 96, 128, 160, 192, 512], input_res=192, z_dim=16, pad=9)
 _MNIST = dict(enc_arch="32b3d2,16b3d2,8b3d2,4b3d4,1b4", dec_arch="1b4,4b4,8b4,16b4,32b4", widths=[16, 32, 64, 128, 256],
-              input_res=32, z_dim=16, wd=0.01)
+              input_res=32, z_dim=16, wd=0.01, pad=4)
 
 HPARAMS_REGISTRY = {
     "morphomnist": dict(hps="morphomnist", parents_x=["thickness", "intensity", "digit"], concat_pa=True,

@@ -115,6 +115,7 @@ class TrainStep:
         self.coef = None
         self.ranges = None
         self.graphs = {}
+        self.inputs = {}  # step_from: (data set, batch size, train, draws tap) -> data.AugmentedInput (static index / parents buffers)
         self.static = None
         self.out3 = None
         self.beta = float(args.beta)
@@ -166,7 +167,7 @@ class TrainStep:
         They live in device memory so that a captured step follows the beta warm-up (trainer.py:57) without re-capture:
         the host rewrites the three floats (outside any capture) only when beta moved.  One tensor per key, kept alive as
         long as the TrainStep: captured graphs hold its address."""
-        B, dims = int(x.shape[0]), float(x[0].numel())
+        B, dims = int(x.shape[0]), float(math.prod(x.shape[1:]))
         ent = self.coefs.get((B, dims))
         if ent is None:
             ent = self.coefs[(B, dims)] = [torch.zeros(3, device=self.eng.device), None]
@@ -178,8 +179,9 @@ class TrainStep:
 
     def _fwd_bwd(self, x, pa, beta):
         m, eng = self.model, self.eng
-        self.coef = self.coefs[(int(x.shape[0]), float(x[0].numel()))][0]  # written by step() before any capture / replay
-        eng.set_loss_scale(int(x.shape[0]) * float(x[0].numel()) * self.accu)
+        dims = float(math.prod(x.shape[1:]))
+        self.coef = self.coefs[(int(x.shape[0]), dims)][0]  # written by step() before any capture / replay
+        eng.set_loss_scale(int(x.shape[0]) * dims * self.accu)
         m.__dict__["_beta_dev"] = self.coef.data_ptr() + 8
         try:
             out3 = m._run_forward(x, pa, beta, record=True)
@@ -375,6 +377,26 @@ class TrainStep:
     # -- public -------------------------------------------------------------------------------------------
     def step(self, x, pa):
         """One optimiser step on a batch already resident on the GPU.  Returns the device tensor [elbo, nll, kl]."""
+        return self._step(x, pa)
+
+    def step_from(self, ds, index, train=True, draws_out=None):
+        """One optimiser step on the rows `index` (device int64 vector) of a ``data.DeviceDataset``: the augmented batch is built
+        inside the step by one ``cgen_batch_augment`` launch -- the first launch after the step's ``rng_advance``, eager and
+        captured alike -- which writes the encoder's input tensor in the compute dtype and a static [B, ctx] parents buffer,
+        drawing crops and flips from the engine's Philox state without advancing it (the step consumes exactly the state
+        advances of ``step()``).  Replays refill a static index buffer, as ``step()`` refills its static batch.  Gradient
+        accumulation, data parallelism and the loss-scale back-off are ``step()``'s.
+        `draws_out` (debug tap): a device int32 [B, 3] tensor that receives the (oy, ox, flip) used; part of the graph key."""
+        key = (id(ds), int(index.numel()), train, None if draws_out is None else draws_out.data_ptr())
+        hook = self.inputs.get(key)
+        if hook is None:
+            from .data import AugmentedInput
+
+            hook = self.inputs[key] = AugmentedInput(ds, int(index.numel()), train, draws_out)
+        hook.load(index)
+        return self._step(hook, hook.pa_buf)
+
+    def _step(self, x, pa):
         a = self.args
         self._loss_scale_check()
         self.it += 1
@@ -390,13 +412,17 @@ class TrainStep:
             drop = type(m.decoder).drop_cond(m.decoder)
             m.decoder.__dict__["drop_cond"] = lambda d=drop: d
         # (beta is device data: the warm-up schedule replays the same graph; virtual and materialised parents are different graphs)
-        key = (tuple(x.shape), x.dtype, drop, do_step, tuple(pa.shape), compact_parents(pa) is not None)
+        static = hasattr(x, "emit")  # a device-side input (step_from): its buffers are static already, its identity keys the graph
+        key = (tuple(x.shape), x.dtype, drop, do_step, tuple(pa.shape), compact_parents(pa) is not None, x.key if static else None)
         ent = self.graphs.get(key)
         self._coef_for(x, beta)
         if ent is None:
             out = self._eager(x, pa, beta, do_step)  # eager warm-up: sizes the arena, builds the tables
-            sx, spb = x.clone(), StaticParents(pa)
-            sp = spb.t
+            if static:
+                sx, spb, sp = x, None, pa
+            else:
+                sx, spb = x.clone(), StaticParents(pa)
+                sp = spb.t
             torch.cuda.synchronize()
             # NCCL inside a captured graph is avoided: under DP the step is graphs around eager all-reduces.  With overlap the
             # backward graph is cut where the decoder half of the gradient is final (engine.on_split): graph A | all-reduce of
@@ -440,7 +466,7 @@ class TrainStep:
             self.graphs[key] = (g1, g2, sx, spb, so, g1b)
             return out
         g1, g2, sx, spb, so, g1b = ent
-        if sx.data_ptr() != x.data_ptr():
+        if not static and sx.data_ptr() != x.data_ptr():
             sx.copy_(x, non_blocking=True)
             spb.load(pa)
         g1.replay()

@@ -838,7 +838,9 @@ class HVAE(nn.Module):
     def _prep_inputs(self, eng, x, parents):
         assert x.dim() == 4 and parents.dim() in (2, 4) and parents.shape[1] == self.context_dim
         xin = None
-        if x is not None:
+        if hasattr(x, "emit"):  # data.AugmentedInput: the batch is built on the device, straight into the encoder's input tensor
+            xin = x.emit(eng)
+        elif x is not None:
             x = x.to(eng.device)
             # raw u8 pixels: trainer.py:17's (x - 127.5) / 127.5 is fused into the layout kernel
             xin = eng.from_nchw(x, rg=False, sub=127.5, mul=1.0 / 127.5) if x.dtype == torch.uint8 else eng.from_nchw(x, rg=False)

@@ -58,7 +58,7 @@ typedef struct cgen_view {
 /* ABI version of this header.  cgen_version() of the loaded library must equal it (causal-gen_amd/_lib.py checks): struct layouts,
  * enum values and signatures are only compatible within one version.  cgen_h16_format(): the 16-bit storage format the library was
  * BUILT for -- 0 = IEEE binary16 (default), 1 = bfloat16 (-DCGEN_H16_BF16, an A/B build); CGEN_F16 tensors must be in that format. */
-#define CGEN_ABI_VERSION 410
+#define CGEN_ABI_VERSION 411
 int cgen_version(void);
 int cgen_h16_format(void);
 const char* cgen_last_error(void);
@@ -312,6 +312,44 @@ int cgen_unary_bwd(int32_t dtype, int32_t op, float param, int32_t n, int32_t h,
                    cgen_view gin, int32_t accumulate, cgen_stream_t);
 /* NHWC view -> contiguous NCHW f32 */
 int cgen_nhwc_to_nchw(int32_t dtype, int32_t n, int32_t c, int32_t h, int32_t w, cgen_view in, float* dst, cgen_stream_t);
+
+/* ------------------------------------------------------------------ device-resident input pipeline (ABI 411; csrc/augment.hip)
+ * One launch builds an augmented training batch from a data set that lives on the device as u8: row gather, zero-padded random
+ * crop, horizontal flip, (v - sub) * mul and the NCHW -> NHWC layout change, written in `dtype`; the parents of the same rows are
+ * gathered on the side.  Replaces the reference's per-sample PIL transforms (src/datasets.py: RandomCrop(input_res, padding) +
+ * RandomHorizontalFlip(p), Pad(2) for evaluation), the host-to-device copy and trainer.py:16-21.
+ *   oy uniform on [0, h0 + 2 pad_y - r_h], ox uniform on [0, w0 + 2 pad_x - r_w]: __umulhi(bits, range + 1) of words 0 / 1 of
+ *   Philox(seed, offset, stream_id, idx = index[b]) -- keyed by the DATA SET ROW, so a row's crop at a given state depends neither on
+ *   its batch position nor on the data-parallel rank that holds it; flip = u01(word 2) < hflip_p (hflip_p = 1 always flips).
+ *   out[b, y, x, ch] = (v - sub) * mul, sx = flip ? r_w - 1 - x : x, iy = oy + y - pad_y, ix = ox + sx - pad_x,
+ *   v = data[index[b], ch, iy, ix] inside the image and 0 outside (u8 padding BEFORE normalisation; crop, then flip: torchvision's order).
+ * The launch reads the Philox state and never advances it.  Addressing into `data` is 64-bit.  A row with index[b] outside
+ * [0, n_data) is never read through: its image is all padding value, its pa_out row zero, its draws_out row (-1, -1, -1).
+ * out: cpad > c asks for zeros in channels [c, cpad) as on cgen_conv2d's output view.  16-byte stores wherever the view allows.
+ * Capturable: no allocation, no synchronisation, one stream. */
+typedef struct cgen_augment_args {
+  int32_t dtype;           /* CGEN_F32 or CGEN_F16 (the 16-bit storage format) */
+  int32_t n, c, h0, w0;    /* batch size; data set images [n_data, c, h0, w0], c in 1..4 */
+  int32_t r_h, r_w;        /* crop (= output) size */
+  int32_t pad_x, pad_y;    /* virtual zero padding left/right and top/bottom */
+  int32_t ctx;             /* parents per row (with pa_data / pa_out) */
+  uint32_t stream_id;      /* Philox stream: no other kernel of a step may use it (the engine passes 980, csrc/common.h) */
+  float hflip_p, sub, mul;
+  int64_t n_data;
+  const void* data;        /* u8 NCHW contiguous */
+  const int64_t* index;    /* device int64[n] */
+  cgen_view out;           /* NHWC [n, r_h, r_w, c] */
+  const uint64_t* rng;     /* device {seed, offset}; may be NULL when draws_in is given */
+  const int32_t* draws_in; /* optional device int32[n][3] = (oy, ox, flip): overrides the draws */
+  int32_t* draws_out;      /* optional, same shape: the draws used */
+  const float* pa_data;    /* optional f32 [n_data][ctx] ... */
+  float* pa_out;           /* ... gathered into f32 [n][ctx] */
+} cgen_augment_args;
+int cgen_batch_augment(const cgen_augment_args* a, cgen_stream_t stream);
+/* Which store arm cgen_batch_augment takes for these arguments, without launching (negative cgen_status when they are invalid):
+ * 0 = contiguous rows, all 16-byte stores; 1 = contiguous rows, 16-byte stores + element-wise row end; 2 = contiguous rows, element-wise
+ * (unaligned view); 3 = one pixel per lane, 16-byte stores (padded pixel stride); 4 = one pixel per lane, element-wise. */
+int cgen_batch_augment_arm(const cgen_augment_args* a);
 
 /* ------------------------------------------------------------------ latent layer (K10, K16)
  * Fused sample_gaussian + gaussian_kl (vae.py:14-30, 268-269):
