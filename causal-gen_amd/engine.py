@@ -16,6 +16,7 @@ import math
 import torch
 
 from . import _lib
+from .pairing import BlockRec, PairSlot, may_pair
 from .wgrad_sched import WgradMixin
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, F16, F32, F32S, NULL_VIEW, UNARY_CLAMP_MIN, UNARY_LEAKY_RELU, View
 
@@ -317,18 +318,17 @@ class Engine(WgradMixin):
         # capped grid, so that they fill the CUs the latency-bound backward chain leaves idle (0: one batch at the end)
         self.wgrad_flush_frac = [float(v) for v in os.environ.get("CGEN_WGRAD_FLUSH_FRAC", "0.7").split(",") if v]
         # Data gradients of two ADJACENT fused Blocks of the tape (a decoder layer's posterior and prior Block) in one launch
-        # (cgen_block3_pair): backward() arms the first one, whose launch is held until the second reaches its own launch point.
+        # (cgen_block3_pair): backward() arms the first one's slot (pairing.PairSlot), which holds its launch until the second
+        # reaches its own launch point.
         self.blk3_pair = os.environ.get("CGEN_BLK3_PAIR", "1") != "0"
-        self._blk3_arm = 0      # 1: the next fused data-gradient launch is to be held; 2: one is held, waiting for its partner
-        self._blk3_hold = None  # (args, launch counter at hold time, tensors touched, the held Block's late bookkeeping)
-        self.blk3_pairs = 0     # pair launches of the last backward pass
+        self._blk3 = PairSlot(self, self._block3_single, lambda h, a: self.lib.block3_pair(C.byref(h), C.byref(a), self.stream),
+                              lambda h, a: self.lib.block3_pair_supported(C.byref(h), C.byref(a)))
         # ... and the same for data-gradient convs on the small-image path (cgen_conv2d_pair): the two gradient outputs of one conv
         # (cat[z, p_feat] of z_feat_proj, cat[h, pa, acts] of an unfused posterior Block), and the second convs of an unfused
         # posterior / prior Block pair, which backward() brings next to each other
         self.conv_pair = os.environ.get("CGEN_CONV_PAIR", "1") != "0"
-        self._conv_arm = 0
-        self._conv_hold = None
-        self.conv_pairs = 0
+        self._conv = PairSlot(self, self._dgrad_single, lambda h, a: self.lib.conv2d_pair(C.byref(h), C.byref(a), self.stream),
+                              lambda h, a: self.lib.conv2d_pair_supported(C.byref(h), C.byref(a)))
         self.wgrad_bg_wgs = int(os.environ.get("CGEN_WGRAD_BG_WGS", "304"))
         self.wgrad_bg_reduce = os.environ.get("CGEN_WGRAD_BG_REDUCE", "1") != "0"
         self._wg_cum, self._wg_total, self._wg_nflush = 0.0, 0.0, 0
@@ -355,8 +355,8 @@ class Engine(WgradMixin):
         self.blk4_launches = 0
         # ... and the data gradients of a decoder layer's posterior and prior Blocks in one launch (cgen_block4_pair), as _bw_block3 does
         self.blk4_pair = os.environ.get("CGEN_BLK4_PAIR", "1") != "0"
-        self.blk4_pairs = 0
-        self._blk4_arm, self._blk4_hold = 0, None
+        self._blk4 = PairSlot(self, self._block4_single, self._block4_pair,
+                              lambda h, a: self.lib.block4_pair_supported(C.byref(h), C.byref(a)))
         # the row-streaming instance (96x96 / 192x192 Blocks, csrc/block.hip blk3r): CGEN_BLK3R=0 off; where it serves a shape the side
         # policy below (blk3_res) does not apply
         self.blk3_rows = int(os.environ.get("CGEN_BLK3R", "1"))
@@ -374,6 +374,11 @@ class Engine(WgradMixin):
         self.split_frac = float(os.environ.get("CGEN_DP_SPLIT_FRAC", "0.8"))
         self.on_split = None
         self.early_final = None
+
+    # pair launches of the last backward pass, per family: kept by the slots
+    blk3_pairs = property(lambda self: self._blk3.pairs, lambda self, v: setattr(self._blk3, "pairs", v))
+    blk4_pairs = property(lambda self: self._blk4.pairs, lambda self, v: setattr(self._blk4, "pairs", v))
+    conv_pairs = property(lambda self: self._conv.pairs, lambda self, v: setattr(self._conv, "pairs", v))
 
     @property
     def trunk_rem(self):
@@ -412,8 +417,8 @@ class Engine(WgradMixin):
         self._wg_events = []
         self._wg_reduced, self._wg_seen = 0, set()
         self._riders = {}
-        self._blk3_arm = self._conv_arm = self._blk4_arm = 0  # (a pass that ended in an exception may have left a launch held)
-        self._blk3_hold = self._conv_hold = self._blk4_hold = None
+        for slot in (self._blk3, self._blk4, self._conv):  # (a pass that ended in an exception may have left a launch held)
+            slot.reset()
         self.pgrad_init = set()
         self._pnhwc, self._pgrad_tmp = {}, {}
         self._adopted = set()
@@ -714,11 +719,8 @@ class Engine(WgradMixin):
         a.res2 = vw(res2)
         a.out_rem = out.rem
         a.res1_rem = res1.rem if res1 is not None else 0
-        if self._ablate and ((site.name.endswith(".conv.1") and "f1" in self._ablate) or ("r12" in self._ablate and x0.h <= 12)
-                             or any(x0.h == r and ("r%d" % r) in self._ablate for r in (24, 48, 96, 192))):
-            pass  # TIMING-ONLY ablation (CGEN_ABLATE, wrong results): the first conv of every Block is not launched
-        else:
-            self._timed("conv_fwd", site, x0, lambda: self.lib.conv2d(C.byref(a), self.stream))
+        if not self._ablated(x0, site, "f1"):  # (f1: the first conv of every Block is not launched)
+            self._timed("conv_fwd", [site], x0, lambda: self.lib.conv2d(C.byref(a), self.stream))
         if self.recording:
             if self._dbg_names is not None:
                 self._dbg_names[id(out.base)] = site.name
@@ -780,106 +782,98 @@ class Engine(WgradMixin):
         sup = self.lib.block3_supported(C.byref(a))
         if not sup or (need_rows and sup != 2):  # (2: the row-streaming instance serves it)
             return None  # (the two tensors just allocated are simply not used: the arena is reset per step)
-        if self._ablate and any(x0.h == r and ("r%d" % r) in self._ablate for r in (24, 48, 96, 192)):
-            pass
-        else:
-            self._timed_blk("conv_fwd", site1, site2, x0, lambda: self.lib.block3(C.byref(a), self.stream))
+        if not self._ablated(x0):
+            self._timed("conv_fwd", (site1, site2), x0, lambda: self.lib.block3(C.byref(a), self.stream))
         if self.recording:
             if self._dbg_names is not None:
                 self._dbg_names[id(out.base)] = site2.name
             if self.blk3_on >= 2:
-                self.tape.append((self._bw_block3, (site1, site2, segs, t, out, res1), self._bw_tag))
+                self.tape.append((self._bw_block3, BlockRec((site1, site2), segs, (t,), out, res1), self._bw_tag))
             else:
                 self.tape.append((self._bw_conv, (site1, segs, ACT_RELU, t, None, None), self._bw_tag))
                 self.tape.append((self._bw_conv, (site2, [t], ACT_RELU, out, res1, None), self._bw_tag))
         return out
 
-    def _bw_block3(self, site1, site2, segs, t, out, res1):
+    def _ablated(self, x0, site=None, tag=None):
+        """TIMING-ONLY ablation (CGEN_ABLATE, wrong results): is this launch skipped?  Resolution tokens (r24 ...) apply to every
+        launch; with a `site` (single convs) also r12 and `tag`: "f1" the first conv of every Block, "d3" the data gradient of its
+        second conv."""
+        ab = self._ablate
+        if not ab:
+            return False
+        if site is not None and ((tag in ab and site.name.endswith({"f1": ".conv.1", "d3": ".conv.3"}[tag])) or ("r12" in ab and x0.h <= 12)):
+            return True
+        return any(x0.h == r and ("r%d" % r) in ab for r in (24, 48, 96, 192))
+
+    def _block3_dgrad_args(self, site1, site2, g, gmid, t, outs):
+        """cgen_block3_args of a light Block's data gradient: grad(out) `g` -> grad(bottleneck) `gmid` (masked by the bottleneck `t`)
+        -> one output per (segment index, target view, forward tensor, view to add or None) of `outs`."""
+        a = _lib.Block3Args()
+        a.dtype, a.n, a.h, a.w, a.nseg, a.nout, a.pre_act = self.dt, g.n, g.h, g.w, 1, len(outs), 0
+        a.seg[0] = g.cv()
+        a.w_a, a.bias_a = site2.frag["a_dg"], None
+        a.w_a16 = site2.frag.get("a16_dg") if self.blk3_rows else None
+        a.mid, a.mid_aux = gmid.cv(), t.cv()
+        for j, (k, gv, sg, prev) in enumerate(outs):
+            a.o[j].w, a.o[j].bias = site1.frag[("b_dg", k)], None
+            a.o[j].out, a.o[j].aux = gv.cv(), sg.cv()
+            a.o[j].res1 = prev.cv() if prev is not None else NULL_VIEW
+        return a
+
+    def _bw_block3(self, sites, segs, mids, out, res1):
         """Backward of a fused light Block: weight gradients as for the two convs (deferred, batched); the two data-gradient
         convs as ONE launch of cgen_block3 (pre_act = 0) -- with two outputs when two segments need a gradient (the posterior
         Block: h and the encoder activation) -- else the two conv launches."""
+        (site1, site2), (t,) = sites, mids
         g = self.grad_read(out)
         if g is None:
-            self._blk3_flush()
+            self._blk3.flush()
             return
         act = ACT_RELU
         dsegs = [k for k, sg in enumerate(segs) if sg.rg and site1.seg_rg[k]]
         ok = (1 <= len(dsegs) <= 2 and "a_dg" in site2.frag and all(("b_dg", k) in site1.frag for k in dsegs)
               and all(segs[k].c % 8 == 0 for k in dsegs) and g.c % 8 == 0)
-        if ok:
-            probe = _lib.Block3Args()
-            probe.dtype, probe.n, probe.h, probe.w, probe.nseg, probe.nout, probe.pre_act = self.dt, g.n, g.h, g.w, 1, len(dsegs), 0
-            probe.seg[0] = g.cv()
-            probe.w_a, probe.bias_a = site2.frag["a_dg"], None
-            probe.w_a16 = site2.frag.get("a16_dg") if self.blk3_rows else None
-            probe.mid, probe.mid_aux = t.cv(), t.cv()
-            for j, k in enumerate(dsegs):
-                sg = segs[k]
-                probe.o[j].w, probe.o[j].bias = site1.frag[("b_dg", k)], None
-                probe.o[j].out, probe.o[j].aux, probe.o[j].res1 = sg.cv(), sg.cv(), NULL_VIEW
+        if ok:  # (a probe on the forward tensors' views: the gradient views are not acquired yet)
+            probe = self._block3_dgrad_args(site1, site2, g, t, t, [(k, segs[k], segs[k], None) for k in dsegs])
             ok = bool(self.lib.block3_supported(C.byref(probe)))
         if not ok:
-            self._blk3_flush()
+            self._blk3.flush()
             self._bw_conv(site2, [t], act, out, res1, None)
             self._bw_conv(site1, segs, act, t, None, None)
             return
         if res1 is not None and res1.rg:
-            self._blk3_flush()  # (a residual Block is never the second of a pair: its residual gradient is a launch of its own)
+            self._blk3.flush()  # (a residual Block is never the second of a pair: its residual gradient is a launch of its own)
+            # (the flush also disarms, so it is never the first either: kept as it is, changing it changes which launches pair)
             self._grad_residual(res1, g, out, [t])
         if self._needs_wgrad(site2) and "wg" not in self._ablate:
             self._wgrad(site2, [t], act, g)
         gt, acc_t = self.grad_write(t)
         assert not acc_t
-        a = _lib.Block3Args()
-        a.dtype, a.n, a.h, a.w, a.nseg, a.nout, a.pre_act = self.dt, g.n, g.h, g.w, 1, len(dsegs), 0
-        a.seg[0] = g.cv()
-        a.w_a, a.bias_a = site2.frag["a_dg"], None
-        a.w_a16 = site2.frag.get("a16_dg") if self.blk3_rows else None
-        a.mid, a.mid_aux = gt.cv(), t.cv()
-        tgt = []
-        for j, k in enumerate(dsegs):
-            sg = segs[k]
-            gv, prev, acc = self._dgrad_target(sg)
-            tgt.append((k, gv, prev, acc))
-            a.o[j].w, a.o[j].bias = site1.frag[("b_dg", k)], None
-            a.o[j].out, a.o[j].aux = gv.cv(), sg.cv()
-            a.o[j].res1 = prev.cv() if acc else NULL_VIEW
+        tgt = [(k,) + self._dgrad_target(segs[k]) for k in dsegs]
+        a = self._block3_dgrad_args(site1, site2, g, gt, t, [(k, gv, segs[k], prev if acc else None) for (k, gv, prev, acc) in tgt])
         x0 = segs[0]
         late = (lambda: self._wgrad(site1, segs, act, gt)) if (self._needs_wgrad(site1) and "wg" not in self._ablate) else (lambda: None)
-        if self._ablate and any(x0.h == r and ("r%d" % r) in self._ablate for r in (24, 48, 96, 192)):
-            self._blk3_flush()
+        if self._ablated(x0):
+            self._blk3.flush()
         elif self.lib.block3_supported(C.byref(a)):
             # tensors this launch writes / reads (storage identity): a pair must not touch each other's
             wr = {id(gt.base)} | {id(gv.base) for (_, gv, _, _) in tgt}
             rd = {id(g.base), id(t.base)} | {id(segs[k].base) for (k, _, _, _) in tgt} | {id(prev.base) for (_, _, prev, acc) in tgt if acc}
-            if self._blk3_arm == 1 and self.prof is None:
-                # held: the partner launches both.  The weight gradient that READS gt is queued only after that launch (a background
-                # flush triggered in between must not see it)
-                self._blk3_hold = (a, self.launches, wr, rd, late, (site1, site2, x0))
-                self._blk3_arm = 2
-                return
-            if self._blk3_hold is not None:
-                ha, hl, hwr, hrd, hlate, hinfo = self._blk3_hold
-                if (hl == self.launches and not (hwr & (wr | rd)) and not (wr & hrd)
-                        and self.lib.block3_pair_supported(C.byref(ha), C.byref(a))):
-                    self._blk3_hold, self._blk3_arm = None, 0
-                    self.lib.block3_pair(C.byref(ha), C.byref(a), self.stream)
-                    self.launches += 1
-                    self.blk3_pairs += 1
-                    hlate()
-                    late()
-                    return
-                self._blk3_flush()
-            self._timed_blk("conv_dgrad", site1, site2, x0, lambda: self.lib.block3(C.byref(a), self.stream))
+            self._blk3.submit(a, wr, rd, (sites, x0), late)
+            return
         else:
             # The REAL gradient views are not served (the probe above saw the forward tensors' views; a gradient buffer may be laid
             # out differently: an out-of-place accumulate target, a copy-on-write -- ADVICE r4): the two data-gradient convs, into
             # the targets already acquired (the bookkeeping above has run and must not run twice)
-            self._blk3_flush()
+            self._blk3.flush()
             self._dgrad_launch(site2, g, t, 0, act, t, gt, gt, False)
             for (k, gv, prev, acc) in tgt:
                 self._dgrad_launch(site1, gt, segs[k], k, act, x0, gv, prev, acc)
         late()
+
+    def _block3_single(self, a, info):
+        sites, x0 = info
+        self._timed("conv_dgrad", sites, x0, lambda: self.lib.block3(C.byref(a), self.stream))
 
     def block4(self, sites, segs, res1=None, trunk=False):
         """A whole default Block -- 1x1(gelu(cat segs)) -> 3x3(gelu) -> 3x3(gelu) -> 1x1(gelu) (+ res1), vae.py:57-71,73-84 -- as ONE
@@ -910,14 +904,14 @@ class Engine(WgradMixin):
         o.w, o.bias = s3.frag["p3_fwd"], (b3.data_ptr() if b3 is not None else None)
         o.out, o.aux, o.res1 = out.cv(), NULL_VIEW, (res1.cv() if res1 is not None else NULL_VIEW)
         o.out_rem, o.res1_rem = out.rem, (res1.rem if res1 is not None else 0)
-        if not self.lib.block4_supported(C.byref(a)):
+        if not self.lib.block4_supported(C.byref(a)):  # (asked AFTER the allocations: kept as it is, moving it is a later change)
             return None
-        self._timed_blk4("conv_fwd", sites, x0, lambda: self.lib.block4(C.byref(a), self.stream))
+        self._timed("conv_fwd", sites, x0, lambda: self.lib.block4(C.byref(a), self.stream))
         self.blk4_launches += 1
         if self.recording:
             if self._dbg_names is not None:
                 self._dbg_names[id(out.base)] = s3.name
-            self.tape.append((self._bw_block4, (sites, segs, tuple(ts), out, res1), self._bw_tag))
+            self.tape.append((self._bw_block4, BlockRec(sites, segs, tuple(ts), out, res1), self._bw_tag))
         return out
 
     def _bw_block4(self, sites, segs, ts, out, res1):
@@ -926,7 +920,7 @@ class Engine(WgradMixin):
         a pair launch with the layer's other Block (cgen_block4_pair; armed by backward())."""
         g = self.grad_read(out)
         if g is None:
-            self._blk4_flush()
+            self._blk4.flush()
             return
         s0, s1, s2, s3 = sites
         t0, t1, t2 = ts
@@ -936,14 +930,15 @@ class Engine(WgradMixin):
         ok = (1 <= len(dsegs) <= 3 and "p0_dg" in s3.frag and "p1_dg" in s2.frag and "p2_dg" in s1.frag
               and all(("p3_dg", k) in s0.frag for k in dsegs) and all(segs[k].c % 8 == 0 for k in dsegs) and g.c % 8 == 0)
         if not ok:
-            self._blk4_flush()
+            self._blk4.flush()
             self._bw_conv(s3, [t2], act, out, res1, None)
             self._bw_conv(s2, [t1], act, t2, None, None)
             self._bw_conv(s1, [t0], act, t1, None, None)
             self._bw_conv(s0, segs, act, t0, None, None)
             return
         if res1 is not None and res1.rg:
-            self._blk4_flush()  # (a residual Block is never the second of a pair: its residual gradient is a launch of its own)
+            self._blk4.flush()  # (a residual Block is never the second of a pair: its residual gradient is a launch of its own)
+            # (the flush also disarms, so it is never the first either: kept as it is, changing it changes which launches pair)
             # (the fused launch reads grad(out) WITH a halo while it writes grad(x): x may adopt grad(out)'s buffer only when its
             #  later accumulation goes out of place -- which is the case exactly when weight gradients are deferred, _dgrad_target)
             self._grad_residual(res1, g, out, [t2] if self._defer_wgrad() else [t2] + list(segs))
@@ -982,50 +977,32 @@ class Engine(WgradMixin):
             wr = {id(g2.base), id(g1.base), id(g0.base)} | {id(gv.base) for (_, gv, _, _) in tgt}
             rd = ({id(g.base), id(t0.base), id(t1.base), id(t2.base)} | {id(segs[k].base) for (k, _, _, _) in tgt}
                   | {id(prev.base) for (_, _, prev, acc) in tgt if acc})
-            if self._blk4_arm == 1 and self.prof is None:
-                self._blk4_hold = (a, self.launches, wr, rd, late, (sites, x0))  # held: the partner launches both
-                self._blk4_arm = 2
-                return
-            if self._blk4_hold is not None:
-                ha, hl, hwr, hrd, hlate, _ = self._blk4_hold
-                if (hl == self.launches and not (hwr & (wr | rd)) and not (wr & hrd)
-                        and self.lib.block4_pair_supported(C.byref(ha), C.byref(a))):
-                    self._blk4_hold, self._blk4_arm = None, 0
-                    self.lib.block4_pair(C.byref(ha), C.byref(a), self.stream)
-                    self.launches += 1
-                    self.blk4_pairs += 1
-                    self.blk4_launches += 1
-                    hlate()
-                    late()
-                    return
-                self._blk4_flush()
-            self._timed_blk4("conv_dgrad", sites, x0, lambda: self.lib.block4(C.byref(a), self.stream))
-            self.blk4_launches += 1
-        else:
-            # the REAL gradient views are not served (an oddly laid-out accumulate target): the four data-gradient convs, into the
-            # targets already acquired (the bookkeeping above has run and must not run twice)
-            self._blk4_flush()
-            self._dgrad_launch(s3, g, t2, 0, act, t2, g2, g2, False)
-            self._dgrad_launch(s2, g2, t1, 0, act, t1, g1, g1, False)
-            self._dgrad_launch(s1, g1, t0, 0, act, t0, g0, g0, False)
-            for (k, gv, prev, acc) in tgt:
-                self._dgrad_launch(s0, g0, segs[k], k, act, x0, gv, prev, acc)
-            self._conv_flush()
+            self._blk4.submit(a, wr, rd, (sites, x0), late)
+            return
+        # the REAL gradient views are not served (an oddly laid-out accumulate target): the four data-gradient convs, into the
+        # targets already acquired (the bookkeeping above has run and must not run twice)
+        self._blk4.flush()
+        self._dgrad_launch(s3, g, t2, 0, act, t2, g2, g2, False)
+        self._dgrad_launch(s2, g2, t1, 0, act, t1, g1, g1, False)
+        self._dgrad_launch(s1, g1, t0, 0, act, t0, g0, g0, False)
+        for (k, gv, prev, acc) in tgt:
+            self._dgrad_launch(s0, g0, segs[k], k, act, x0, gv, prev, acc)
+        self._conv.flush()
         late()
 
-    def _blk4_flush(self):
-        """Launch a held fused default-Block data gradient on its own (its partner did not come, or cannot share the launch)."""
-        self._blk4_arm = 0
-        if self._blk4_hold is None:
-            return
-        ha, _, _, _, hlate, (sites, x0) = self._blk4_hold
-        self._blk4_hold = None
-        self._timed_blk4("conv_dgrad", sites, x0, lambda: self.lib.block4(C.byref(ha), self.stream))
+    def _block4_single(self, a, info):
+        sites, x0 = info
+        self._timed("conv_dgrad", sites, x0, lambda: self.lib.block4(C.byref(a), self.stream))
         self.blk4_launches += 1
-        hlate()
 
-    def _timed_blk4(self, kind, sites, x0, fn):
-        """A fused default-Block launch, tallied (when profiling) with the algorithmic FLOPs of the FOUR convs it executes."""
+    def _block4_pair(self, held, a):
+        self.lib.block4_pair(C.byref(held), C.byref(a), self.stream)
+        self.blk4_launches += 1  # (a pair counts once)
+
+    def _timed(self, kind, sites, x0, fn, ci=None):
+        """Launch `fn`, which executes the convs `sites`; when profiling, bracket it with events on the launch stream and tally
+        algorithmic FLOPs (2 * Ci * k*k * Co per output pixel and conv) under (kind, shape) -- (kind + "_blk", ...) for a fused Block.
+        `ci`: the input channels a single conv actually reads (the data gradient of one segment)."""
         self.launches += 1
         if self.prof is None:
             return fn()
@@ -1033,52 +1010,12 @@ class Engine(WgradMixin):
         e0.record()
         fn()
         e1.record()
-        flops = 2.0 * sum(st.ci * st.taps * st.co for st in sites) * x0.n * x0.h * x0.w
-        ent = self.prof.setdefault((kind + "_blk", 3, sites[0].ci, sites[3].co, x0.h), [0.0, [], 0])
-        ent[0] += flops
-        ent[1].append((e0, e1))
-        ent[2] += 1
-
-    def _blk3_flush(self):
-        """Launch a held fused data gradient on its own (its partner did not come, or cannot share the launch)."""
-        self._blk3_arm = 0
-        if self._blk3_hold is None:
-            return
-        ha, _, _, _, hlate, (s1, s2, x0) = self._blk3_hold
-        self._blk3_hold = None
-        self._timed_blk("conv_dgrad", s1, s2, x0, lambda: self.lib.block3(C.byref(ha), self.stream))
-        hlate()
-
-    def _timed(self, kind, site, x0, fn, ci=None):
-        """Launch `fn`; when profiling, bracket it with events on the launch stream and tally algorithmic FLOPs
-        (2 * Ci * k*k * Co per output pixel) under (kind, shape)."""
-        self.launches += 1
-        if self.prof is None:
-            return fn()
-        ci = site.ci if ci is None else ci
-        flops = 2.0 * ci * site.taps * site.co * x0.n * x0.h * x0.w
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        key = (kind, site.ks, ci, site.co, x0.h)
+        first = sites[0]
+        ci = first.ci if ci is None else ci
+        macs = ci * first.taps * first.co + sum(st.ci * st.taps * st.co for st in sites[1:])
+        key = (kind, first.ks, ci, first.co, x0.h) if len(sites) == 1 else (kind + "_blk", 3, ci, sites[-1].co, x0.h)
         ent = self.prof.setdefault(key, [0.0, [], 0])
-        ent[0] += flops
-        ent[1].append((e0, e1))
-        ent[2] += 1
-
-    def _timed_blk(self, kind, site1, site2, x0, fn):
-        """A fused Block launch, tallied (when profiling) with the algorithmic FLOPs of BOTH convs it executes."""
-        self.launches += 1
-        if self.prof is None:
-            return fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        flops = 2.0 * (site1.ci * site1.taps * site1.co + site2.ci * site2.taps * site2.co) * x0.n * x0.h * x0.w
-        ent = self.prof.setdefault((kind + "_blk", 3, site1.ci, site2.co, x0.h), [0.0, [], 0])
-        ent[0] += flops
+        ent[0] += 2.0 * macs * x0.n * x0.h * x0.w
         ent[1].append((e0, e1))
         ent[2] += 1
 
@@ -1090,7 +1027,7 @@ class Engine(WgradMixin):
             return self.conv(site, [self.im2col(x, site.im2col)], ACT_NONE)
         out = self.new(x.n, x.h, x.w, site.co)
         b = site.conv.bias
-        self._timed("conv_fwd", site, x, lambda: self.lib.stem_conv_fwd(
+        self._timed("conv_fwd", [site], x, lambda: self.lib.stem_conv_fwd(
             self.dt, x.n, x.h, x.w, site.ci, site.ks, site.co, x.cv(), site.conv.weight.data_ptr(), b.data_ptr() if b is not None else None,
             out.cv(), self.stream))
         if self.recording:
@@ -1506,14 +1443,18 @@ class Engine(WgradMixin):
         return gv
 
     # ------------------------------------------------------------------ backward
+    def _entry_sites(self, fn, a):
+        """(conv site, a tensor of its image size) of every conv that tape entry (fn, a, tag) runs the backward of."""
+        if fn == self._bw_conv:
+            yield a[0], a[1][0]
+        elif fn == self._bw_block3 or fn == self._bw_block4:
+            for st in a.sites:
+                yield st, a.segs[0]
+
     def backward(self):
         if self.wgrad_flush_frac:  # total weight-gradient work of this pass: the background-flush marks are fractions of it
-            self._wg_total = sum(2.0 * a[0].ci * a[0].taps * a[0].co * a[1][0].n * a[1][0].h * a[1][0].w
-                                 for fn, a, _ in self.tape if fn == self._bw_conv and self._needs_wgrad(a[0]))
-            self._wg_total += sum(2.0 * st.ci * st.taps * st.co * a[2][0].n * a[2][0].h * a[2][0].w
-                                  for fn, a, _ in self.tape if fn == self._bw_block3 for st in a[:2] if self._needs_wgrad(st))
-            self._wg_total += sum(2.0 * st.ci * st.taps * st.co * a[1][0].n * a[1][0].h * a[1][0].w
-                                  for fn, a, _ in self.tape if fn == self._bw_block4 for st in a[0] if self._needs_wgrad(st))
+            self._wg_total = sum(2.0 * st.ci * st.taps * st.co * x0.n * x0.h * x0.w
+                                 for fn, a, _ in self.tape for st, x0 in self._entry_sites(fn, a) if self._needs_wgrad(st))
         main_t = torch.cuda.current_stream(self.device)
         if self._side_join_pending:  # side-stream work of the forward pass nobody has joined yet (the stem's im2col)
             self.join_side()
@@ -1522,59 +1463,38 @@ class Engine(WgradMixin):
         tape = self.tape
         for i in range(len(tape) - 1, -1, -1):
             fn, args, _ = tape[i]
-            if fn == self._bw_block3:
-                self._blk4_flush()
-                # (armed when the NEXT entry is a fused Block of the same image size without a residual: the layer's prior Block)
-                nxt = tape[i - 1] if i > 0 else None
-                # ... and reads none of this Block's differentiable inputs: else its bookkeeping (an accumulate target, a
-                # copy-on-write of the shared gradient) could launch work that must see this Block's result first
-                if (self.blk3_pair and self._blk3_hold is None and nxt is not None and nxt[0] == self._bw_block3
-                        and nxt[1][5] is None and nxt[1][2][0].h == args[2][0].h and nxt[1][2][0].w == args[2][0].w
-                        and not ({id(v.base) for v in args[2] if v.rg} & {id(v.base) for v in nxt[1][2] if v.rg})
-                        and not any(v.base is nxt[1][4].base for v in args[2])):
-                    self._blk3_arm = 1
+            if fn == self._bw_block3 or fn == self._bw_block4:
+                slot, other, on = (self._blk3, self._blk4, self.blk3_pair) if fn == self._bw_block3 else (self._blk4, self._blk3, self.blk4_pair)
+                other.flush()
+                if on and slot.held is None and may_pair(tape[i], tape[i - 1] if i > 0 else None):
+                    slot.arm()
                 fn(*args)
-                if self._blk3_arm == 1:  # (it did not reach its launch point)
-                    self._blk3_arm = 0
-            elif fn == self._bw_block4:
-                self._blk3_flush()
-                # (armed when the NEXT entry is a fused default Block of the same image size without a residual -- the layer's prior
-                #  Block -- that reads none of this Block's differentiable inputs nor its output: the rule of the light Blocks above)
-                nxt = tape[i - 1] if i > 0 else None
-                if (self.blk4_pair and self._blk4_hold is None and nxt is not None and nxt[0] == self._bw_block4
-                        and nxt[1][4] is None and nxt[1][1][0].h == args[1][0].h and nxt[1][1][0].w == args[1][0].w
-                        and not ({id(v.base) for v in args[1] if v.rg} & {id(v.base) for v in nxt[1][1] if v.rg})
-                        and not any(v.base is nxt[1][3].base for v in args[1])):
-                    self._blk4_arm = 1
-                fn(*args)
-                if self._blk4_arm == 1:  # (it did not reach its launch point)
-                    self._blk4_arm = 0
+                slot.disarm()  # (if still armed: it did not reach its launch point)
             else:
-                self._blk3_flush()
-                self._blk4_flush()
+                self._blk3.flush()
+                self._blk4.flush()
                 if skip:
                     skip -= 1
                     continue
                 if self.conv_pair and fn == self._bw_conv and self.dt != F32 and self._two_unfused_blocks(i):
                     # X.conv2 | Y.conv2 in one launch, then X.conv1, Y.conv1 (their own gradient outputs pair inside _bw_conv)
-                    self._conv_arm = 1
+                    self._conv.arm()
                     fn(*args)
-                    if self._conv_arm == 1:
-                        self._conv_arm = 0
+                    self._conv.disarm()
                     y2, x1, y1 = tape[i - 2], tape[i - 1], tape[i - 3]
                     y2[0](*y2[1])
-                    self._conv_flush()
+                    self._conv.flush()
                     x1[0](*x1[1])
-                    self._conv_flush()
+                    self._conv.flush()
                     y1[0](*y1[1])
-                    self._conv_flush()
+                    self._conv.flush()
                     skip = 3
                     continue
                 fn(*args)
-                self._conv_flush()
-        self._blk3_flush()
-        self._blk4_flush()
-        self._conv_flush()
+                self._conv.flush()
+        self._blk3.flush()
+        self._blk4.flush()
+        self._conv.flush()
         for bid in list(self._riders):
             gv, g, acc = self._riders.pop(bid)
             self.lib.axpby(self.dt, g.n, g.h, g.w, g.cv(), gv.cv(), 1.0, 1.0, 1 << 30, 1 if acc else 0, self.stream)
@@ -1598,12 +1518,12 @@ class Engine(WgradMixin):
         if self._needs_wgrad(site) and "wg" not in self._ablate:  # ("wg": timing-only ablation, no weight gradients at all)
             self._wgrad(site, segs, act, g)
         todo = [k for k, s in enumerate(segs) if s.rg and site.seg_rg[k]]
-        if self.conv_pair and len(todo) >= 2 and self._conv_hold is None and self._conv_arm == 0 and self.dt != F32:
-            self._conv_arm = 1  # the first of this conv's data gradients waits for the second (independent outputs, same input)
+        if self.conv_pair and len(todo) >= 2 and not self._conv.busy and self.dt != F32:
+            self._conv.arm()  # the first of this conv's data gradients waits for the second (independent outputs, same input)
         for k in todo:
             self._dgrad_one(site, g, segs[k], k, act, x0)
         if len(todo) >= 2:
-            self._conv_flush()
+            self._conv.flush()
 
     def _dgrad_one(self, site, g, s, k, act, x0):
         gv, prev, acc = self._dgrad_target(s)
@@ -1621,36 +1541,18 @@ class Engine(WgradMixin):
         a.aux = vw(s) if act != ACT_NONE else NULL_VIEW
         a.res1 = vw(prev) if acc else NULL_VIEW
         a.res2 = NULL_VIEW
-        if self._ablate and ((site.name.endswith(".conv.3") and "d3" in self._ablate) or ("r12" in self._ablate and x0.h <= 12)
-                             or any(x0.h == r and ("r%d" % r) in self._ablate for r in (24, 48, 96, 192))):
-            return  # TIMING-ONLY ablation: the data gradient of every Block's second conv is not launched
-        if self._conv_arm or self._conv_hold is not None:
+        if self._ablated(x0, site, "d3"):  # (d3: the data gradient of every Block's second conv is not launched)
+            return
+        if self._conv.busy:
             wr = {id(gv.base)}
             rd = {id(g.base), id(s.base)} | ({id(prev.base)} if acc else set())
-            if self._conv_arm == 1 and self.prof is None:
-                self._conv_hold = (a, self.launches, wr, rd, (site, x0, s.c))
-                self._conv_arm = 2
-                return
-            if self._conv_hold is not None:
-                ha, hl, hwr, hrd, _ = self._conv_hold
-                if (hl == self.launches and not (hwr & (wr | rd)) and not (wr & hrd)
-                        and self.lib.conv2d_pair_supported(C.byref(ha), C.byref(a))):
-                    self._conv_hold, self._conv_arm = None, 0
-                    self.lib.conv2d_pair(C.byref(ha), C.byref(a), self.stream)
-                    self.launches += 1
-                    self.conv_pairs += 1
-                    return
-                self._conv_flush()
-        self._timed("conv_dgrad", site, x0, lambda: self.lib.conv2d(C.byref(a), self.stream), ci=s.c)
+            self._conv.submit(a, wr, rd, (site, x0, s.c))
+        else:
+            self._dgrad_single(a, (site, x0, s.c))
 
-    def _conv_flush(self):
-        """Launch a held data-gradient conv on its own (no partner came, or it cannot share a launch)."""
-        self._conv_arm = 0
-        if self._conv_hold is None:
-            return
-        ha, _, _, _, (site, x0, ci) = self._conv_hold
-        self._conv_hold = None
-        self._timed("conv_dgrad", site, x0, lambda: self.lib.conv2d(C.byref(ha), self.stream), ci=ci)
+    def _dgrad_single(self, a, info):
+        site, x0, ci = info
+        self._timed("conv_dgrad", [site], x0, lambda: self.lib.conv2d(C.byref(a), self.stream), ci=ci)
 
     def _two_unfused_blocks(self, i):
         """tape[i], [i-1] = conv2, conv1 of Block X and tape[i-2], [i-3] = conv2, conv1 of Block Y (backward order), both unfused,

@@ -52,7 +52,7 @@ class WgradMixin:
             self._wg_cum += cost
             self._wgrad_marks()
         else:
-            self._timed("conv_wgrad", site, x0, lambda: self.lib.conv2d_wgrad(C.byref(a), self.stream))
+            self._timed("conv_wgrad", [site], x0, lambda: self.lib.conv2d_wgrad(C.byref(a), self.stream))
         self._wg_events.append((site, key, nsplit))
 
     def _wgrad_marks(self):

@@ -213,7 +213,13 @@ def test_fused_block3_remainder_planes(shape):
     assert d <= 0.02 * float(outs[0][1][0].abs().max()), d  # (a bottleneck value within rounding of an f16 boundary may round the other way)
 
 
-def _run_two(N, H, W, b, segA, rgA, coA, segB, rgB, coB, pair, seed=0, fuse=2, chain=False, share=False):
+# what a profiled backward pass of _run_two tallied before the engine's three timing functions became one (the batched weight
+# gradients go under one key of their own)
+PROF_KEYS_FUSED = {("conv_dgrad_blk", 3, 128, 160, 24), ("conv_dgrad_blk", 3, 260, 32, 24), ("conv_wgrad", 0, 0, 0, 0)}
+PROF_KEYS_UNFUSED = {("conv_dgrad", 3, 40, 32, 12), ("conv_dgrad", 3, 40, 192, 12), ("conv_dgrad", 3, 160, 40, 12), ("conv_wgrad", 0, 0, 0, 0)}
+
+
+def _run_two(N, H, W, b, segA, rgA, coA, segB, rgB, coB, pair, seed=0, fuse=2, chain=False, share=False, prof=None):
     """Two independent light Blocks recorded back to back (the posterior and the prior Block of a decoder layer, vae.py:240-301), one
     backward pass: with `pair` their data gradients share a launch (cgen_block3_pair)."""
     from causal_gen_amd.engine import ConvSite, Engine
@@ -260,7 +266,9 @@ def _run_two(N, H, W, b, segA, rgA, coA, segB, rgB, coB, pair, seed=0, fuse=2, c
         gy = eng.seed_grad(y)
         eng.lib.axpby(eng.dt, N, H, W, eng.from_nchw(gouts[k].cuda()).cv(), gy.cv(), 1.0, 1.0, 1 << 30, 0, eng.stream)
     eng.recording = False
+    eng.prof = prof  # (a dict: the backward pass is profiled per launch, which rules out held launches)
     eng.backward()
+    eng.prof = None
     torch.cuda.synchronize()
     out = []
     for k, t in nts:
@@ -286,6 +294,23 @@ def test_block3_pair_launch_is_bit_identical_to_two_launches(shape):
     print("pair launches:", pb)
     if shape[0] != 3:
         assert pb == 1
+
+
+@pytest.mark.parametrize("fuse,shape,keys", [
+    (2, (8, 24, 24, 32, [128, 4, 128], [1, 0, 1], 32, [128], [1], 160), PROF_KEYS_FUSED),
+    (0, (32, 12, 12, 40, [160, 4, 160], [1, 0, 1], 32, [160, 4], [1, 0], 192), PROF_KEYS_UNFUSED),
+], ids=["fused-24x24", "unfused-12x12"])
+def test_a_profiled_backward_pass_holds_no_launch(fuse, shape, keys):
+    """Profiling brackets every launch with events of its own, so nothing is held and nothing pairs: same bits as the pair run, and
+    the tallies carry the keys bench.py reads -- (kind, ks, ci, co, h) per conv, (kind + "_blk", 3, ci of the first conv, co of
+    the last, h) per fused Block; the literals are what the engine recorded before the three timing functions became one."""
+    a, pa = _run_two(*shape, pair=True, fuse=fuse)
+    prof = {}
+    b, pb = _run_two(*shape, pair=True, fuse=fuse, prof=prof)
+    assert pa > 0 and pb == 0, (pa, pb)
+    for x, y in zip(a, b):
+        assert torch.equal(x, y), float((x - y).abs().max())
+    assert set(prof) == keys
 
 
 @pytest.mark.parametrize("shape", [

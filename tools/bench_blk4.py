@@ -33,7 +33,7 @@ def run(shape, fuse):
     cs = [torch.nn.Conv2d(ci, b, 1), torch.nn.Conv2d(b, b, 3, padding=1), torch.nn.Conv2d(b, b, 3, padding=1), torch.nn.Conv2d(b, co, 1)]
     eng = Engine("cuda", "f16")
     eng.wgrad_flush_frac = []
-    eng._ablate = "wg"
+    eng._ablate = frozenset({"wg"})
     holder = torch.nn.ModuleList(cs).cuda()
     sites = [ConvSite("c0", holder[0], segc, [bool(r) for r in segrg], 0)] + [ConvSite(f"c{k}", holder[k], [b], [True], k) for k in (1, 2, 3)]
     for r in range(4):
