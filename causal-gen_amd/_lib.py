@@ -77,6 +77,13 @@ class PredHead(C.Structure):
                 ("reserved", C.c_int32), ("w", C.c_void_p * 8), ("b", C.c_void_p * 8), ("y", C.c_void_p), ("obs", C.c_void_p)]
 
 
+class PredTrainHead(C.Structure):
+    """cgen_pred_train_head: ``hd`` with the RAW weights in hd.w (hd.b[7] = fc.3's bias), the seven BatchNorms and every gradient."""
+    _fields_ = [("hd", PredHead), ("gamma", C.c_void_p * 7), ("beta", C.c_void_p * 7), ("running_mean", C.c_void_p * 7),
+                ("running_var", C.c_void_p * 7), ("num_batches_tracked", C.c_void_p * 7), ("gw", C.c_void_p * 8), ("gb", C.c_void_p),
+                ("ggamma", C.c_void_p * 7), ("gbeta", C.c_void_p * 7)]
+
+
 class AugmentArgs(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("c", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32), ("r_h", C.c_int32),
                 ("r_w", C.c_int32), ("pad_x", C.c_int32), ("pad_y", C.c_int32), ("ctx", C.c_int32), ("stream_id", C.c_uint32),
@@ -173,6 +180,9 @@ PROTOTYPES = {
     "cgen_predictor_tiled_workspace": [C.POINTER(PredHead), i32, i32, C.POINTER(i64)],
     "cgen_predictor_tiled_fwd": [C.POINTER(PredHead), i32, i32, vp, vp, i64, vp, vp, vp, vp],
     "cgen_predictor_tiled_bwd": [C.POINTER(PredHead), i32, i32, vp, vp, i64, vp, vp, vp],
+    "cgen_predictor_train_workspace": [C.POINTER(PredTrainHead), i32, i32, C.POINTER(i64)],
+    "cgen_predictor_train_fwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, f32, vp, vp, vp, vp],
+    "cgen_predictor_train_bwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, vp, vp, vp],
     "cgen_philox_normal": [vp, i64, vp, u32, vp],
     "cgen_rng_advance": [vp, u64, vp],
 }

@@ -4,7 +4,8 @@
 // the activation stack of a head lives in LDS (fused path, 32x32 presets: 88 KiB at C = 1, 96 KiB at C = 3) or in a caller-owned
 // global workspace.  The convolutions are VALU FMA loops: at B = 256 the whole morphomnist forward is ~2 GMAC, the launch is
 // latency-bound.  Tiled (second half of this file): one launch per layer over (tile x channel group x image x head), for the
-// large images whose 32 workgroups would leave the chip idle.
+// large images whose 32 workgroups would leave the chip idle.  Training mode (batch-statistic BatchNorm, parameter gradients) is
+// predictor_train.inc, included at the end of this file: it shares the geometry, the likelihoods and the tiled data gradients.
 //
 // Backward recomputes the head's forward, then walks back IN PLACE: the gradient of a layer's output overwrites that layer's
 // post-activation once its LeakyReLU mask has been read (LeakyReLU keeps the sign, so the post-activation is the mask).  The
@@ -895,21 +896,29 @@ int tile_forward(const char* fn, const TileArgs& p, hipStream_t st) {
   return check_launch(fn);
 }
 
-int tile_backward(const char* fn, const TileArgs& p, hipStream_t st) {
-  const PredGeo g = pred_geo(p.hd[0]);
+// data gradient of 3x3 layer L into the planes of layer L - 1 (the stem's, through the pool, for L == 1)
+void tile_bwd_layer(const TileArgs& p, const PredGeo& g, int L, hipStream_t st) {
   const int64_t pairs = (int64_t)p.n * p.nheads;
-  for (int L = 5; L >= 1; --L) {
-    const TileLayer ly = tile_layer(g, L);
-    const int ct = tile_ct(ly.cin), nb = (ly.hin + ly.s - 1) / ly.s, nt = (nb + 7) / 8;
-    const int64_t blocks = pairs * (ly.cin / (4 * ct)) * nt * nt;
-    const bool pool = L == 1 && g.pool;
-    TILE_CT_SWITCH(ct, if (ly.s == 1) TILE_LAUNCH((ptile_conv_bwd<1, CT, 0>), blocks, p, L);
-                   else if (pool) TILE_LAUNCH((ptile_conv_bwd<2, CT, 1>), blocks, p, L);
-                   else TILE_LAUNCH((ptile_conv_bwd<2, CT, 0>), blocks, p, L));
-  }
+  const TileLayer ly = tile_layer(g, L);
+  const int ct = tile_ct(ly.cin), nb = (ly.hin + ly.s - 1) / ly.s, nt = (nb + 7) / 8;
+  const int64_t blocks = pairs * (ly.cin / (4 * ct)) * nt * nt;
+  const bool pool = L == 1 && g.pool;
+  TILE_CT_SWITCH(ct, if (ly.s == 1) TILE_LAUNCH((ptile_conv_bwd<1, CT, 0>), blocks, p, L);
+                 else if (pool) TILE_LAUNCH((ptile_conv_bwd<2, CT, 1>), blocks, p, L);
+                 else TILE_LAUNCH((ptile_conv_bwd<2, CT, 0>), blocks, p, L));
+}
+
+// dx from the stem's planes
+void tile_bwd_stem(const TileArgs& p, const PredGeo& g, hipStream_t st) {
   const int nb = (g.r + g.s1 - 1) / g.s1, nt = (nb + 15) / 16;
   if (g.s1 == 2) TILE_LAUNCH((ptile_stem_bwd<2>), (int64_t)p.n * nt * nt, p);
   else TILE_LAUNCH((ptile_stem_bwd<1>), (int64_t)p.n * nt * nt, p);
+}
+
+int tile_backward(const char* fn, const TileArgs& p, hipStream_t st) {
+  const PredGeo g = pred_geo(p.hd[0]);
+  for (int L = 5; L >= 1; --L) tile_bwd_layer(p, g, L, st);
+  tile_bwd_stem(p, g, st);
   return check_launch(fn);
 }
 
@@ -1005,3 +1014,5 @@ extern "C" int cgen_predictor_tiled_bwd(const cgen_pred_head* heads, int32_t nhe
   if (rc) return rc;
   return tile_backward("cgen_predictor_tiled_bwd", p, (hipStream_t)stream);
 }
+
+#include "predictor_train.inc"

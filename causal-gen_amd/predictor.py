@@ -6,6 +6,8 @@ fine-tuning (train_cf.py:123-124, dscm.py:23-24): every BatchNorm is a per-chann
 linear (refreshed when a parameter or buffer changes), and each PGM's image heads run in ONE HIP launch per direction
 (csrc/predictor.hip; one launch per LAYER on the tiled path that large images take, see ``_choose_path``): the trunk, the spatial
 mean, the head MLP and the per-variable log-likelihood of flow_pgm.py's ``model_anticausal``.  Only the input gradient exists: ``d aux / d cf_x`` is what flows on into the HVAE.
+(Training these predictors -- batch-statistic BatchNorm, parameter gradients, the optimiser step -- is ``predictor_train.PredictorTrainStep``;
+nothing here has a training mode.)
 
 ``model_anticausal(**obs)`` returns the summed negative log-likelihood (what pyro's ``Trace_ELBO.differentiable_loss`` of the
 anticausal model with the empty guide computes); ``AnticausalELBO`` hands it to ``DSCM.forward`` as ``elbo_fn``.

@@ -534,6 +534,42 @@ int cgen_predictor_tiled_fwd(const cgen_pred_head* heads, int32_t nheads, int32_
 int cgen_predictor_tiled_bwd(const cgen_pred_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, int64_t ws_floats,
                              const float* coef_dev, float* dx, cgen_stream_t);
 
+/* ------------------------------------------------------------------ anticausal predictors, TRAINING mode (additive in ABI 411)
+ * The same CNN with batch-statistic BatchNorm (pgm/layers.py CNN in train mode; train_pgm.py sup_epoch, --setup sup_aux): the
+ * forward, the gradient of every parameter and, optionally, of the image.  One launch per layer over the whole batch, on the
+ * activation layout of the tiled placement; same shapes as cgen_predictor_tiled_supported.  Per conv layer the forward writes
+ * the raw convolution z (no bias, no activation), reduces the per-channel batch mean and BIASED variance over n*h*h in two
+ * passes over z (mean first, then sum (z - mean)^2: no cancellation), writes a = lrelu(gamma (z - mean) invstd + beta) and
+ * updates running_mean / running_var as nn.BatchNorm2d does (momentum, unbiased variance N / (N - 1), num_batches_tracked += 1).
+ * The tail (spatial mean, cat y, fc.0, BatchNorm1d over the n images, LeakyReLU, fc.3, the likelihood) sees all images of a head.
+ * A record: `hd` as for the eval paths except that hd.w[0..7] are the RAW weights (six convs, fc.0, fc.3), hd.b[7] is fc.3's
+ * bias and hd.b[0..6] are not read; BatchNorm i = 0..5 follows conv i, BatchNorm 6 is fc.1.
+ * The backward uses the state the forward left in ws (it does NOT recompute the forward: the running statistics move once per
+ * step) and may be run once per forward.  Every gradient is OVERWRITTEN with coef_dev[0] * d(sum of terms)/d(parameter); all
+ * reductions run in a fixed order without atomics: reruns are bit-identical.  Every launch goes on `stream`; no host
+ * synchronisation, allocation or read of device data (capturable).  n >= 2 (BatchNorm1d needs more than one value per channel). */
+typedef struct cgen_pred_train_head {
+  cgen_pred_head hd;
+  const float* gamma[7];            /* BatchNorm weight */
+  const float* beta[7];             /* BatchNorm bias */
+  float* running_mean[7];
+  float* running_var[7];
+  int64_t* num_batches_tracked[7];
+  float* gw[8];                     /* gradients of hd.w[0..7] */
+  float* gb;                        /* gradient of fc.3's bias */
+  float* ggamma[7];
+  float* gbeta[7];
+} cgen_pred_train_head;
+/* floats of workspace for n images: two activation stacks (pre-BatchNorm and post-activation) per (image, head), the batch
+ * statistics, the tail's per-image rows and the partial sums of the split weight gradients */
+int cgen_predictor_train_workspace(const cgen_pred_train_head* heads, int32_t nheads, int32_t n, int64_t* floats);
+/* terms / outs / loss as cgen_predictor_fwd (terms is required); momentum = BatchNorm's (0.1) */
+int cgen_predictor_train_fwd(const cgen_pred_train_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, int64_t ws_floats,
+                             float momentum, float* terms, float* outs, float* loss, cgen_stream_t);
+/* dx (optional, NCHW like x) = coef_dev[0] * d(sum of terms)/dx; same heads, n, x and ws as the forward just run */
+int cgen_predictor_train_bwd(const cgen_pred_train_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, int64_t ws_floats,
+                             const float* coef_dev, float* dx, cgen_stream_t);
+
 /* ------------------------------------------------------------------ step tail (K17; trainer.py:67-87, utils.py:178-225)
  * Flat-buffer fused global-norm -> clip -> skip predicate -> AdamW -> EMA.
  * state_dev: f32[8] = {sum_sq, grad_norm, clip_coef, skip_flag, n_skipped, opt_steps, n_skipped_nonfinite, -}.  LambdaLR warm-up, Adam
