@@ -92,6 +92,19 @@ class AugmentArgs(C.Structure):
                 ("pa_data", C.c_void_p), ("pa_out", C.c_void_p)]
 
 
+class MetricVar(C.Structure):
+    """cgen_metric_var: one variable of cgen_metric_accum (kind, transform, in-place prediction / target rows, the accumulator block)."""
+    _fields_ = [("kind", C.c_int32), ("transform", C.c_int32), ("ncls", C.c_int32), ("reserved", C.c_int32), ("pred", C.c_void_p),
+                ("pred_stride", C.c_int64), ("target", C.c_void_p), ("target_stride", C.c_int64), ("pred_scale", C.c_float),
+                ("pred_shift", C.c_float), ("tgt_scale", C.c_float), ("tgt_shift", C.c_float), ("norm", C.c_float),
+                ("reserved2", C.c_int32), ("acc", C.c_void_p), ("scores", C.c_void_p), ("labels", C.c_void_p),
+                ("capacity", C.c_int64), ("row_count", C.c_void_p)]
+
+
+METRIC_BINARY, METRIC_CATEGORICAL, METRIC_CONTINUOUS = 0, 1, 2
+METRIC_NONE, METRIC_SIGMOID, METRIC_SOFTMAX, METRIC_TANH = 0, 1, 2, 3
+METRIC_N, METRIC_CORRECT, METRIC_ABS_ERR, METRIC_SKIPPED, METRIC_OVERFLOW = 0, 1, 2, 3, 4
+METRIC_MAX_VARS, METRIC_ACC = 8, 8
 STREAM_AUGMENT = 980  # Philox stream id of cgen_batch_augment (the list of taken ids is in csrc/common.h)
 PRED_NORMAL, PRED_CATEGORICAL, PRED_BERNOULLI = 0, 1, 2
 PRED_MAX_HEADS, PRED_MAX_OUT = 4, 16
@@ -183,6 +196,9 @@ PROTOTYPES = {
     "cgen_predictor_train_workspace": [C.POINTER(PredTrainHead), i32, i32, C.POINTER(i64)],
     "cgen_predictor_train_fwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, f32, vp, vp, vp, vp],
     "cgen_predictor_train_bwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, vp, vp, vp],
+    "cgen_metric_accum": [C.POINTER(MetricVar), i32, i32, vp],
+    "cgen_rocauc": [vp, vp, vp, i64, i32, i64, vp, vp, vp],
+    "cgen_image_dist": [i32, i64, vp, vp, vp, vp, vp, vp],
     "cgen_philox_normal": [vp, i64, vp, u32, vp],
     "cgen_rng_advance": [vp, u64, vp],
 }

@@ -328,6 +328,18 @@ class _AnticausalPredictor(nn.Module):
         outs = _run_outputs(heads, obs, self.std_fixed, owner=self)
         return {hd.var: o for hd, o in zip(heads, outs)}
 
+    def _host_outputs(self, obs) -> Dict[str, Tensor]:
+        return {}
+
+    @torch.no_grad()
+    def raw_outputs(self, **obs) -> Dict[str, Tensor]:
+        """What ``predict`` starts from, before its sigmoid / softmax / tanh: {variable: [B, nout] raw head outputs}, each a view
+        (row stride CGEN_PRED_MAX_OUT) into the forward launch's output buffer, plus the locs of the host-side heads
+        (``FlowPredictor``: "age").  ``cf_eval.MetricAccumulator.update_from`` hands these rows to the metric kernel in place."""
+        out = self._outputs(obs)
+        out.update(self._host_outputs(obs))
+        return out
+
     def load_reference_state_dict(self, sd: Dict[str, Tensor]):
         """Load the anticausal predictors of a reference PGM checkpoint (train_cf.py:302-308 loads a whole FlowPGM as the predictor):
         exactly its ``encoder_*`` keys, strictly; the parent mechanisms' keys are dropped and returned (pgm.py loads those)."""
@@ -415,6 +427,9 @@ class FlowPredictor(_AnticausalPredictor):
         a_loc, a_logscale = self._age(obs)
         age = obs["age"].reshape(a_loc.shape).float().to(a_loc.device)
         return -torch.distributions.Normal(a_loc, self.f(a_logscale)).log_prob(age).sum()
+
+    def _host_outputs(self, obs) -> Dict[str, Tensor]:
+        return {"age": self._age(obs)[0]}
 
     def predict(self, **obs) -> Dict[str, Tensor]:
         o = self._outputs(obs)

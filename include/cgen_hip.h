@@ -570,6 +570,67 @@ int cgen_predictor_train_fwd(const cgen_pred_train_head* heads, int32_t nheads, 
 int cgen_predictor_train_bwd(const cgen_pred_train_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, int64_t ws_floats,
                              const float* coef_dev, float* dx, cgen_stream_t);
 
+/* ------------------------------------------------------------------ counterfactual evaluation (additive in ABI 411: new symbols only, no struct, enum value or signature moved)
+ * The numbers of the reference's evaluation half, accumulated on the device: train_cf.py:63-108 get_metrics over the predictions
+ * the `else` branch of cf_epoch collects (train_cf.py:181-189), and train_pgm.py:175-249 eval_epoch on factual images -- ROC-AUC
+ * and accuracy of the binary / categorical predictors, mean absolute error of the continuous ones -- plus the per-image distances
+ * behind the composition and reversibility measures.  The reference pulls every batch to the host and calls sklearn.
+ * All three calls only enqueue on `stream`: no allocation, no host read of device data, no global state (capturable).  Every
+ * result is bit-identical from run to run: sums are reduced in a fixed order in f64, pair counts are 64-bit INTEGER atomics
+ * (order-independent); there is no floating-point atomic.  Arguments are checked before anything is launched. */
+#define CGEN_METRIC_MAX_VARS 8
+#define CGEN_METRIC_ACC 8 /* doubles per accumulator block */
+enum cgen_metric_kind { CGEN_METRIC_BINARY = 0, CGEN_METRIC_CATEGORICAL = 1, CGEN_METRIC_CONTINUOUS = 2 };
+/* what predict() applies to the raw head output (flow_pgm.py predict: sigmoid / softmax / tanh / nothing) */
+enum cgen_metric_transform { CGEN_METRIC_NONE = 0, CGEN_METRIC_SIGMOID = 1, CGEN_METRIC_SOFTMAX = 2, CGEN_METRIC_TANH = 3 };
+enum cgen_metric_slot { CGEN_METRIC_N = 0,        /* rows counted */
+                        CGEN_METRIC_CORRECT = 1,  /* BINARY / CATEGORICAL: rows predicted right */
+                        CGEN_METRIC_ABS_ERR = 2,  /* CONTINUOUS: sum of |target - prediction| / norm */
+                        CGEN_METRIC_SKIPPED = 3,  /* rows with a non-finite prediction or target (cf_epoch's NaN `continue`) */
+                        CGEN_METRIC_OVERFLOW = 4  /* counted rows that did not fit in the score buffer (left out of the AUC only) */ };
+typedef struct cgen_metric_var {
+  int32_t kind;          /* cgen_metric_kind */
+  int32_t transform;     /* cgen_metric_transform: BINARY NONE / SIGMOID, CATEGORICAL NONE / SOFTMAX, CONTINUOUS NONE / TANH */
+  int32_t ncls;          /* columns read: BINARY / CONTINUOUS 1, CATEGORICAL 2..CGEN_PRED_MAX_OUT */
+  int32_t reserved;
+  const float* pred;     /* [n][pred_stride], ncls columns read: e.g. one head of cgen_predictor_fwd's `outs` in place
+                            (pred_stride = CGEN_PRED_MAX_OUT), or any [n, k] tensor */
+  int64_t pred_stride;   /* floats, >= ncls */
+  const float* target;   /* [n][target_stride]: BINARY 0 / 1, CATEGORICAL a one-hot row of ncls, CONTINUOUS 1 value */
+  int64_t target_stride; /* floats, >= ncls (CATEGORICAL) or >= 1 */
+  /* CONTINUOUS: |(t * tgt_scale + tgt_shift) - (f(o) * pred_scale + pred_shift)| / norm, in f64 (get_metrics' unnormalisation) */
+  float pred_scale, pred_shift, tgt_scale, tgt_shift, norm;
+  int32_t reserved2;
+  double* acc;           /* [CGEN_METRIC_ACC], indexed by cgen_metric_slot; this call ADDS to it */
+  /* AUC (optional, BINARY / CATEGORICAL; all NULL = no AUC): rows are appended in sample order at *row_count.
+   * BINARY: score = sigmoid(o) (f32; o itself with NONE), label = t > 0.5.  CATEGORICAL: the softmax row (the row itself with
+   * NONE) and the one-hot row.  Row r, column c sits at [r * ncls + c]. */
+  float* scores;
+  float* labels;
+  int64_t capacity;      /* rows the two buffers hold */
+  int64_t* row_count;    /* device: rows appended so far (<= capacity) */
+} cgen_metric_var;
+/* One batch of n samples, one record per variable (1..CGEN_METRIC_MAX_VARS), one launch.  Per sample: BINARY correct iff
+ * (o > 0) == (t > 0.5) with SIGMOID -- torch.round(sigmoid(o)) == t including o == 0 -> 0 -- or (p > 0.5) == (t > 0.5) with NONE;
+ * CATEGORICAL correct iff argmax(pred) == argmax(target), first maximum wins (train_cf.py:98); CONTINUOUS as above.  A row with
+ * a non-finite prediction or target is skipped for that variable; a row beyond `capacity` is dropped from the AUC only. */
+int cgen_metric_accum(const cgen_metric_var* vars, int32_t nvars, int32_t n, cgen_stream_t);
+/* Exact ROC-AUC per column, (#{s+ > s-} + 0.5 #{s+ == s-}) / (n+ n-) over all positive / negative pairs (what
+ * sklearn.metrics.roc_auc_score computes, train_cf.py:73,87,100): a tiled O(n^2) pair count through LDS with 64-bit integer
+ * counts -- exact, order-independent, no sort.  scores / labels: [rows][stride], `ncls` columns read (binary: 1; the one-vs-rest
+ * macro AUC of train_cf.py:100-105 is the caller's mean over columns); label > 0.5 is a positive; rows with a NaN score are left
+ * out.  The row count is min(*n_rows_dev, n_rows_max), read on the device; n_rows_max (host, < 2^31) only sizes the grid.
+ * auc_out[ncls] (f64): NaN for a column without a positive or without a negative.  ws: 4 * ncls uint64, zeroed by the call. */
+int cgen_rocauc(const float* scores, const float* labels, const int64_t* n_rows_dev, int64_t n_rows_max, int32_t ncls,
+                int64_t stride, double* auc_out, uint64_t* ws, cgen_stream_t);
+/* Per-image distances of two NCHW f32 batches of n images, elems_per_image floats each (contiguous): L1 = mean |a - b| and
+ * L2 = mean (a - b)^2, the differences and sums in f64 throughout.  One workgroup reduces one image in a fixed order (16-byte
+ * loads when both bases and the image size allow, else a scalar path) into ws[i] = {L1, L2} (f64 [n][2], required) and, if
+ * given, per_image[i] = the same rounded to f32; a second launch folds the n values in a fixed order and ADDS
+ * {sum L1, sum L2, n} to acc[3] (optional). */
+int cgen_image_dist(int32_t n, int64_t elems_per_image, const float* a, const float* b, float* per_image, double* ws, double* acc,
+                    cgen_stream_t);
+
 /* ------------------------------------------------------------------ step tail (K17; trainer.py:67-87, utils.py:178-225)
  * Flat-buffer fused global-norm -> clip -> skip predicate -> AdamW -> EMA.
  * state_dev: f32[8] = {sum_sq, grad_norm, clip_coef, skip_flag, n_skipped, opt_steps, n_skipped_nonfinite, -}.  LambdaLR warm-up, Adam
