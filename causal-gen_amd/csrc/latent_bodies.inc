@@ -112,6 +112,26 @@ __device__ __forceinline__ void reparam_ride_item(const LatBwdP& p, const int64_
   st8(p.ride_dst, o, v);
 }
 
+// the four head gradients of 8 consecutive channels (first one `ch`) of one pixel, from values already in registers: k0 = the
+// sample's KL coefficient, gz = d/dz (read only when has_gz), zv = z.  Shared by the stand-alone kernel below and the fused
+// backward latent tail (latent_tail.hip), whose d/dz comes straight from its MFMA accumulators.
+__device__ __forceinline__ void reparam_kl_bwd_vec8_math(const float k0, const float* chan_scale, const int ch, const float logt, const bool has_gz,
+                                                         const float (&ql)[8], const float (&qs)[8], const float (&pl)[8], const float (&ps)[8],
+                                                         const float (&gz)[8], const float (&zv)[8], float (&o1)[8], float (&o2)[8],
+                                                         float (&o3)[8], float (&o4)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float kk = k0 * (chan_scale ? chan_scale[ch + k] : 1.f);
+    const float q = qs[k] + logt, pp = ps[k] + logt;
+    const float e2q = expf(2.f * q), ie2p = expf(-2.f * pp), d = ql[k] - pl[k];
+    float gql = kk * d * ie2p, gqs = kk * (e2q * ie2p - 1.f);
+    o3[k] = -kk * d * ie2p;
+    o4[k] = kk * (1.f - (e2q + d * d) * ie2p);
+    if (has_gz) { gql += gz[k]; gqs += gz[k] * (zv[k] - ql[k]); }
+    o1[k] = gql; o2[k] = gqs;
+  }
+}
+
 // main item g (8-channel group index over [n][h][w][c / 8]): the four head gradients of one group
 __device__ __forceinline__ void reparam_kl_bwd_vec8_item(const LatBwdP& p, const int64_t g) {
   const int per8 = (p.h * p.w * p.c) >> 3, cg = p.c >> 3;
@@ -129,17 +149,7 @@ __device__ __forceinline__ void reparam_kl_bwd_vec8_item(const LatBwdP& p, const
   }
   const float k0 = p.coef[(int64_t)b * p.coef_stride];
   float o1[8], o2[8], o3[8], o4[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const float kk = k0 * (p.chan_scale ? p.chan_scale[ch + k] : 1.f);
-    const float q = qs[k] + p.logt, pp = ps[k] + p.logt;
-    const float e2q = expf(2.f * q), ie2p = expf(-2.f * pp), d = ql[k] - pl[k];
-    float gql = kk * d * ie2p, gqs = kk * (e2q * ie2p - 1.f);
-    o3[k] = -kk * d * ie2p;
-    o4[k] = kk * (1.f - (e2q + d * d) * ie2p);
-    if (p.gz.p) { gql += gz[k]; gqs += gz[k] * (zv[k] - ql[k]); }
-    o1[k] = gql; o2[k] = gqs;
-  }
+  reparam_kl_bwd_vec8_math(k0, p.chan_scale, ch, p.logt, p.gz.p != nullptr, ql, qs, pl, ps, gz, zv, o1, o2, o3, o4);
   const int a1 = off8(p.g_q_loc, b, y, x, ch), a2 = off8(p.g_q_ls, b, y, x, ch), a3 = off8(p.g_p_loc, b, y, x, ch), a4 = off8(p.g_p_ls, b, y, x, ch);
   if (p.acc_q) {
     float t[8];

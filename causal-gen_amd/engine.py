@@ -329,6 +329,14 @@ class Engine(WgradMixin):
         self.conv_pair = os.environ.get("CGEN_CONV_PAIR", "1") != "0"
         self._conv = PairSlot(self, self._dgrad_single, lambda h, a: self.lib.conv2d_pair(C.byref(h), C.byref(a), self.stream),
                               lambda h, a: self.lib.conv2d_pair_supported(C.byref(h), C.byref(a)))
+        # A stochastic decoder layer's backward latent tail -- the 1x1 data gradients of z_feat_proj and z_proj and the reparam backward,
+        # three adjacent tape entries -- as ONE launch (cgen_latent_tail_bwd; _latent_tail_at / _bw_latent_tail).  0: the four launches.
+        self.lat_tail = os.environ.get("CGEN_LAT_TAIL", "1") != "0"
+        self.lat_tail_minpx = int(os.environ.get("CGEN_LAT_TAIL_MINPX", "0"))  # layers with fewer pixels (n * h * w) keep the four launches
+        # its arithmetic: by default the four launches' own, bit for bit (every GEMM summed and rounded to binary16 where they store
+        # grad(z) / grad(p_feat)); 1: one f32 sum and one rounding per output -- closer to exact, and no longer the same bits
+        self.lat_tail_exact = os.environ.get("CGEN_LAT_TAIL_EXACT", "0") != "0"
+        self.lat_tails = 0  # fused launches of the last backward()
         self.wgrad_bg_wgs = int(os.environ.get("CGEN_WGRAD_BG_WGS", "304"))
         self.wgrad_bg_reduce = os.environ.get("CGEN_WGRAD_BG_REDUCE", "1") != "0"
         self._wg_cum, self._wg_total, self._wg_nflush = 0.0, 0.0, 0
@@ -1458,7 +1466,7 @@ class Engine(WgradMixin):
         main_t = torch.cuda.current_stream(self.device)
         if self._side_join_pending:  # side-stream work of the forward pass nobody has joined yet (the stem's im2col)
             self.join_side()
-        self.blk3_pairs = self.conv_pairs = self.blk4_pairs = 0
+        self.blk3_pairs = self.conv_pairs = self.blk4_pairs = self.lat_tails = 0
         skip = 0
         tape = self.tape
         for i in range(len(tape) - 1, -1, -1):
@@ -1476,6 +1484,11 @@ class Engine(WgradMixin):
                 if skip:
                     skip -= 1
                     continue
+                if self.lat_tail and fn == self._bw_conv and self.dt == F16 and self.prof is None:
+                    ents = self._latent_tail_at(i)
+                    if ents is not None and self._bw_latent_tail(*ents):
+                        skip = (2 if ents[0] is not None else 1)
+                        continue
                 if self.conv_pair and fn == self._bw_conv and self.dt != F32 and self._two_unfused_blocks(i):
                     # X.conv2 | Y.conv2 in one launch, then X.conv1, Y.conv1 (their own gradient outputs pair inside _bw_conv)
                     self._conv.arm()
@@ -1573,6 +1586,94 @@ class Engine(WgradMixin):
         if {id(v.base) for v in g1 if v.rg} & {id(v.base) for v in g3 if v.rg}:  # both would accumulate into one gradient
             return False
         return s0.ks == s2.ks
+
+    def _latent_tail_at(self, i):
+        """tape[i], [i-1], [i-2] = z_feat_proj, z_proj, reparam of one stochastic decoder layer (backward order; a layer without
+        z_feat_proj: tape[i], [i-1] = z_proj, reparam): returns their argument tuples (None for an absent z_feat_proj), else None.
+        Recognised by structure alone: two 1x1 convs without activation that read the reparam's z as their first segment, z_proj adding
+        a channel slice of the prior Block's output (p_feat) as a residual, z_feat_proj reading that same slice as its second segment."""
+        tape = self.tape
+
+        def conv_at(j):
+            if j < 0 or tape[j][0] != self._bw_conv:
+                return None
+            site, segs, act, out, r1, r2 = tape[j][1]
+            return tape[j][1] if site.ks == 1 and act == ACT_NONE and len(segs) == 2 and segs[0].rg and site.seg_rg[0] else None
+
+        a, f = conv_at(i), None
+        if a is None:
+            return None
+        if a[4] is None and a[5] is None:  # no residuals: z_feat_proj, with z_proj behind it
+            a, f, i = conv_at(i - 1), a, i - 1
+            if a is None or f[1][0] is not a[1][0] or not (f[1][1].rg and f[0].seg_rg[1]):
+                return None
+        if i < 1 or tape[i - 1][0] != self._bw_reparam:
+            return None
+        r = tape[i - 1][1]
+        q_loc, q_ls, p_loc, p_ls, z = r[:5]
+        site, segs, _, out, r1, r2 = a
+        zd = z.c
+        if segs[0] is not z or (segs[1].rg and site.seg_rg[1]) or not all(t.rg for t in (q_loc, q_ls, p_loc, p_ls)):
+            return None
+        pb, qb = p_loc.base, q_loc.base
+        slices = ((q_loc, qb, 0), (q_ls, qb, zd), (p_loc, pb, 0), (p_ls, pb, zd))
+        if pb is qb or any(t.base is not b or t.coff != o or t.c != zd for t, b, o in slices) or qb.c < 2 * zd:
+            return None
+        pf = [t for t in (r1, r2) if t is not None and t.base is pb]  # the residual that is p_feat
+        if len(pf) != 1 or not pf[0].rg or pf[0].coff != 2 * zd or pf[0].c != site.co or pb.c != 2 * zd + site.co:
+            return None
+        if f is not None and (f[1][1].base is not pb or f[1][1].coff != 2 * zd or f[1][1].c != site.co):
+            return None
+        return f, a, r
+
+    def _bw_latent_tail(self, f, a, r):
+        """The three entries _latent_tail_at found as one cgen_latent_tail_bwd launch.  Returns False -- nothing done, the caller runs
+        the four launches -- when the kernel does not serve the shapes or a gradient buffer involved may not be written in place."""
+        q_loc, q_ls, p_loc, p_ls, z, logt, fb_col, coef_ptr = r
+        site_z, segs_z, _, out_z, r1, r2 = a
+        zd, c = z.c, site_z.co
+        if self._ablate or z.n * z.h * z.w < self.lat_tail_minpx:
+            return False
+        pall, qall = p_loc.base.chan(0, 2 * zd + c), q_loc.base.chan(0, 2 * zd)
+        if self._frozen(pall) or self._frozen(qall) or id(p_loc.base) in self._riders or id(q_loc.base) in self._riders:
+            return False
+        g_h = self.grad_read(out_z)
+        if g_h is None:
+            return False
+        g_f = self.grad_read(f[3]) if f is not None else None
+        gz_in = self.grad_read(z)
+        t = _lib.LatentTailArgs()
+        t.dtype, t.n, t.h, t.w, t.z_dim, t.c = self.dt, z.n, z.h, z.w, zd, c
+        t.coef_stride, t.logt, t.parity = 0, logt, 0 if self.lat_tail_exact else 1
+        t.g_h = g_h.cv()
+        t.g_f = g_f.cv() if g_f is not None else NULL_VIEW
+        t.gz_in = gz_in.cv() if gz_in is not None else NULL_VIEW
+        t.q_loc, t.q_ls, t.p_loc, t.p_ls, t.z = q_loc.cv(), q_ls.cv(), p_loc.cv(), p_ls.cv(), z.cv()
+        # (the views grad_write will hand out below: _gentry creates the buffers, as the four launches' grad_write would)
+        t.out_p = self._gentry(p_loc.base)[0].chan(0, 2 * zd + c).cv()
+        t.out_q = self._gentry(q_loc.base)[0].chan(0, 2 * zd).cv()
+        if g_f is not None:
+            t.img_fz, t.img_fp = f[0].img_dg[0], f[0].img_dg[1]
+        t.img_pz = site_z.img_dg[0]
+        t.coef = self.kl_coef_ptr if coef_ptr is None else coef_ptr
+        t.chan_scale = None if fb_col is None else self.kl_chan_ptr + 4 * fb_col
+        if not self.lib.latent_tail_bwd_supported(C.byref(t)):
+            return False
+        # ---- committed: the bookkeeping of the three entries, in their order
+        if g_f is not None and self._needs_wgrad(f[0]):
+            self._wgrad(f[0], f[1], ACT_NONE, g_f)
+        for res in (r1, r2):
+            if res is not None and res.rg and res.base is not p_loc.base:  # (p_feat's share of G_h is added by the kernel)
+                self._grad_residual(res, g_h, out_z, segs_z)
+        if self._needs_wgrad(site_z):
+            self._wgrad(site_z, segs_z, ACT_NONE, g_h)
+        gp, acc_p = self.grad_write(pall)
+        gq, acc_q = self.grad_write(qall)
+        t.out_p, t.out_q, t.acc_p, t.acc_q = gp.cv(), gq.cv(), 1 if acc_p else 0, 1 if acc_q else 0
+        self.lib.latent_tail_bwd(C.byref(t), self.stream)
+        self.launches += 1
+        self.lat_tails += 1
+        return True
 
     def _dgrad_target(self, s):
         """Where the data gradient of input tensor `s` goes: (view to write, view to add when accumulating, accumulate?)."""

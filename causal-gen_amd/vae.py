@@ -797,9 +797,12 @@ class HVAE(nn.Module):
             # side strand of backward() (it reads the gradient the prior Block's backward wrote), so it sits late; and it stays in
             # FRONT of z_proj's backward, whose residual copy into grad(p_feat) then still rides on the reparam backward (a rider
             # parked before another writer of that buffer would have to land as a launch of its own: +5.6 us per layer, measured)
-            eng.tape[t_zp:t_zp] = hold
+            # (launched here or early on the side stream, its tape entry sits in the same place: z_feat_proj, z_proj and the reparam are
+            # adjacent in backward(), which runs the three as one launch -- Engine._latent_tail_at.  Its data gradients touch nothing the
+            # conv Block's backward touches.)
             if feat:
-                z = eng.conv(self._site(eng, blk.z_feat_proj), [z_cur, p_feat], ACT_NONE)
+                z = eng.conv(self._site(eng, blk.z_feat_proj), [z_cur, p_feat], ACT_NONE, tape_hold=hold)
+            eng.tape[t_zp:t_zp] = hold
         if side_ahead:
             eng.join_side()
         return h, out

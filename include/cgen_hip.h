@@ -400,6 +400,38 @@ int cgen_mediator_mix(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c,
                       cgen_view q_ls, cgen_view p_loc, cgen_view p_ls, float alpha, float t, float logt, int32_t linear_var, cgen_view out,
                       cgen_stream_t);
 
+/* ------------------------------------------------------------------ backward latent tail of a decoder layer (additive in ABI 411: new symbols only)
+ * One launch (csrc/latent_tail.hip; binary16) for what follows a stochastic decoder layer's conv Block in the backward pass
+ * (vae.py:263-300): the data gradients of z_feat_proj w.r.t. z and p_feat, the data gradient of z_proj w.r.t. z, the residual's
+ * share of grad(p_feat) and the reparameterisation / KL backward.  With G_h = grad(h') [C channels] and G_f = grad(zf) [g_f.c]:
+ *   g_z     = W_p[:, :Z]^T G_h + W_f[:, :Z]^T G_f + gz_in           (in registers, never stored; see `parity`)
+ *   g_pfeat = G_h + W_f[:, Z:]^T G_f
+ *   g_q_loc, g_q_ls, g_p_loc, g_p_ls: cgen_reparam_kl_bwd's formulas with d/dz = g_z
+ *   out_p = [g_p_loc | g_p_ls | g_pfeat]  (2Z + C channels)       out_q = [g_q_loc | g_q_ls]  (2Z channels)
+ * acc_p / acc_q: add what out_p / out_q already hold.  g_f.p == NULL: the layer has no z_feat_proj (g_pfeat = G_h); gz_in.p == NULL: none.
+ * Weights: the data-gradient images cgen_weight_prep (mode 1) writes -- img_fz / img_fp = the z / p_feat segment of z_feat_proj
+ * (rows x (ceil32(g_f.c) + 32)), img_pz = the z segment of z_proj (rows x (ceil32(C) + 32)); img_fz / img_fp are not read without g_f.
+ * Served (cgen_latent_tail_bwd_supported() == 1, answered without a GPU): CGEN_F16; Z in {8, 16}; C and g_f.c multiples of 32 up to
+ * 192; every view 16-byte aligned, linear in pixels (sn == h * sh, sh == w * sw) and below 2^31 bytes.  Anything else:
+ * _supported() == 0 and cgen_latent_tail_bwd returns CGEN_EUNSUPPORTED without launching. */
+typedef struct cgen_latent_tail_bwd_args {
+  int32_t dtype, n, h, w, z_dim, c;
+  int32_t coef_stride, acc_q, acc_p;
+  float logt;
+  int32_t parity;   /* 0: one f32 sum and ONE binary16 rounding per output; 1: bit for bit what cgen_conv2d (x3) +
+                     * cgen_reparam_kl_bwd_rider leave -- each GEMM summed in the order of the kernel cgen_conv2d picks for the
+                     * shape and rounded to binary16 where those launches store grad(z) / grad(p_feat) (the engine's default) */
+  int32_t reserved;
+  cgen_view g_h, g_f, gz_in;            /* [n,h,w,C], [n,h,w,g_f.c] or absent, [n,h,w,Z] or absent */
+  cgen_view q_loc, q_ls, p_loc, p_ls, z; /* [n,h,w,Z] each */
+  cgen_view out_p, out_q;               /* [n,h,w,2Z + C], [n,h,w,2Z] */
+  const void *img_fz, *img_fp, *img_pz;
+  const float* coef;       /* kl_coef_dev[b * coef_stride], as in cgen_reparam_kl_bwd */
+  const float* chan_scale; /* optional [Z] */
+} cgen_latent_tail_bwd_args;
+int cgen_latent_tail_bwd_supported(const cgen_latent_tail_bwd_args* a);
+int cgen_latent_tail_bwd(const cgen_latent_tail_bwd_args* a, cgen_stream_t stream);
+
 /* ------------------------------------------------------------------ likelihoods (K11-K14) and ELBO
  * Discretised Gaussian (vae.py:352-411).  params view holds [loc(C) | logscale(C) | coeff(3, only C==3)] per pixel
  * (the raw 1x1-conv outputs); x is NHWC.  For C == 3 a params view of >= 9 channels selects vae.py's autoregressive
