@@ -110,6 +110,17 @@ class MetricVar(C.Structure):
                 ("capacity", C.c_int64), ("row_count", C.c_void_p)]
 
 
+class PgmMech(C.Structure):
+    """cgen_pgm_mech: one mechanism of the parent SCM (kind, the columns it scores and conditions on, its MLP / spline geometry,
+    its parameters and their gradient slots)."""
+    _fields_ = [("kind", C.c_int32), ("normalize", C.c_int32), ("col", C.c_int32), ("ncls", C.c_int32), ("nctx", C.c_int32),
+                ("ctx_col", C.c_int32 * 2), ("nhidden", C.c_int32), ("width", C.c_int32 * 3), ("act", C.c_int32), ("bins", C.c_int32),
+                ("bound", C.c_float), ("p", C.c_void_p * 8), ("g", C.c_void_p * 8)]
+
+
+PGM_BERNOULLI, PGM_CATEGORICAL, PGM_SPLINE, PGM_AFFINE, PGM_GUMBEL_MAX = 0, 1, 2, 3, 4
+PGM_LEAKY_RELU, PGM_GELU, PGM_SIGMOID = 0, 1, 2
+PGM_MAX_MECH, PGM_MAX_WIDTH, PGM_MAX_HIDDEN, PGM_MAX_BINS, PGM_MAX_CLS, PGM_ROWS = 8, 64, 3, 8, 16, 64
 METRIC_BINARY, METRIC_CATEGORICAL, METRIC_CONTINUOUS = 0, 1, 2
 METRIC_NONE, METRIC_SIGMOID, METRIC_SOFTMAX, METRIC_TANH = 0, 1, 2, 3
 METRIC_N, METRIC_CORRECT, METRIC_ABS_ERR, METRIC_SKIPPED, METRIC_OVERFLOW = 0, 1, 2, 3, 4
@@ -207,6 +218,9 @@ PROTOTYPES = {
     "cgen_predictor_train_workspace": [C.POINTER(PredTrainHead), i32, i32, C.POINTER(i64)],
     "cgen_predictor_train_fwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, f32, vp, vp, vp, vp],
     "cgen_predictor_train_bwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, vp, vp, vp],
+    "cgen_pgm_workspace": [C.POINTER(PgmMech), i32, i32, C.POINTER(i64)],
+    "cgen_pgm_nll_fwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp],
+    "cgen_pgm_nll_fwd_bwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp, vp, i64, vp],
     "cgen_metric_accum": [C.POINTER(MetricVar), i32, i32, vp],
     "cgen_rocauc": [vp, vp, vp, i64, i32, i64, vp, vp, vp],
     "cgen_image_dist": [i32, i64, vp, vp, vp, vp, vp, vp],

@@ -17,7 +17,9 @@ with f = linear rational spline (pyro ``T.Spline(1, count_bins=4, order="linear"
 (layers.py:33-43: ``loc + exp(log_scale) * eps`` with (loc, log_scale) = DenseNN(context)), the [-1, 1] normalisation
 ``2 sigmoid(.) - 1``, and -- for discrete mechanisms -- the Gumbel-max posterior of layers.py:107-171.
 
-Scalars only; there is no kernel here (a few floats per sample, host-side torch).  The parameter / module names follow
+Scalars only; the mechanisms here are host-side torch (a few floats per sample).  ``log_prob`` / ``nll`` are the density the
+reference trains the SCM on (``train_pgm.py --setup sup_pgm``); ``pgm_train.PgmTrainStep`` trains it on the GPU (csrc/pgm.hip)
+and is checked against ``log_prob`` in f64.  The parameter / module names follow
 the reference's so that its ``state_dict`` keys load: ``load_reference_state_dict`` takes a reference PGM checkpoint, drops the
 anticausal predictors the reference keeps on the same module (``encoder_*``: CNN / ResNet heads used by ``train_pgm.py`` and the
 classifier guide, outside this path -- SURVEY 8f-3) and loads everything else strictly.
@@ -29,7 +31,7 @@ reproduces the observed class.  The spline follows Dolatabadi et al. 2020 ("Inve
 rational splines") as implemented by pyro 1.8 (``_monotonic_rational_spline``), restated from its published formulae.
 """
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -171,6 +173,25 @@ class LinearSpline(nn.Module):
         x = th * (x1 - x0) + x0
         return torch.where(inside, x, y)
 
+    def inv_and_log_det(self, y: Tensor):
+        """(x, log|dy/dx|(x)) with x = inv(y), for the density of a spline-transformed variable.  Both pieces of a bin are
+        linear-fractional in theta, y = N(theta) / D(theta), so dy/dtheta = w_a w_c lambda (y_c - y_k) / D^2 on the left piece and
+        w_b w_c (1 - lambda) (y_{k+1} - y_c) / D^2 on the right one, and dy/dx = dy/dtheta / (x_{k+1} - x_k); 1 outside the bound.
+        The piece is selected BEFORE every division, so the branch not taken contributes neither values nor gradients."""
+        inside = (y > -self.bound) & (y < self.bound)
+        ycl = y.clamp(-self.bound, self.bound)
+        yk = self._knots()[1]
+        idx = self._bin(ycl, yk)
+        x0, x1, y0, y1, lm, wa, wb, wc, yc = self._coeffs(idx)
+        left = ycl <= yc
+        th = torch.where(left, lm * wa * (y0 - ycl), wc * (yc - ycl) + lm * wb * (ycl - y1)) / \
+            torch.where(left, wa * (y0 - ycl) + wc * (ycl - yc), wc * (yc - ycl) + wb * (ycl - y1))
+        den = torch.where(left, wa * (lm - th) + wc * th, wc * (1.0 - th) + wb * (th - lm))
+        num = torch.where(left, wa * wc * lm * (yc - y0), wb * wc * (1.0 - lm) * (y1 - yc))
+        x = th * (x1 - x0) + x0
+        log_det = torch.log(num / (den * den) / (x1 - x0))
+        return torch.where(inside, x, y), torch.where(inside, log_det, torch.zeros_like(log_det))
+
 
 # ----------------------------------------------------------------------------- Gumbel-max mechanism (layers.py:107-171)
 def gumbel_max_forward(gumbels: Tensor, logits: Tensor) -> Tensor:
@@ -207,10 +228,75 @@ def gumbel_max_abduct_exact(k: Tensor, logits: Tensor, generator: Optional[torch
 
 
 # ----------------------------------------------------------------------------- the two parent SCMs
+class Mechanism(NamedTuple):
+    """One factor of p(parents): the variable it scores, its kind, the module (or root parameter) that holds its parameters, the
+    variables its context is made of (in the order ``model()`` concatenates them) and whether the variable lives in [-1, 1] behind
+    ``normalize_fwd``.  ``log_prob`` on the host and ``PgmTrainStep`` on the device are both driven by this list."""
+    var: str
+    kind: str  # "bernoulli" | "categorical" | "spline" | "affine" | "gumbel_max"
+    module: object
+    ctx: Tuple[str, ...] = ()
+    normalize: bool = False
+
+
+HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+
+
+def _unnormalize(x: Tensor, normalize: bool):
+    """(u, the log-density term of the [-1, 1] normalisation): u = normalize_inv(x) and -(log 2 + logsigmoid(u) + logsigmoid(-u)),
+    i.e. minus the log-derivative of 2 sigmoid(u) - 1; (x, 0) for a variable that is not normalised."""
+    if not normalize:
+        return x, torch.zeros_like(x)
+    u = normalize_inv(x)
+    return u, -(math.log(2.0) + F.logsigmoid(u) + F.logsigmoid(-u))
+
+
 class _BasePGM(nn.Module):
     """Abduction / action / prediction over a small DAG of flow mechanisms (BasePGM.counterfactual, flow_pgm.py:71-108)."""
     variables: Dict[str, str] = {}
     order: List[str] = []
+
+    def mechanisms(self) -> List[Mechanism]:
+        raise NotImplementedError
+
+    def log_prob(self, obs: Dict[str, Tensor]) -> Dict[str, Tensor]:
+        """log p(variable | its parents) per row, one [B] tensor per variable: the terms ``svi_model`` scores under an empty guide
+        (train_pgm.py ``--setup sup_pgm``).  Plain differentiable torch on any device and dtype.
+        Bernoulli root: x l - softplus(l).  Categorical root: sum(onehot * log_softmax(logits)).  Spline flow on Normal(0, 1):
+        -eps^2/2 - log(2 pi)/2 - log|d spline / d eps|(eps) with eps = spline.inv(u).  Conditional affine: the same with
+        eps = (u - loc) exp(-log_scale) and log_scale for the log-derivative.  Gumbel-max (TransformedDistributionGumbelMax.log_prob,
+        layers.py:203-217): log_softmax(logits(ctx))[class]; the base Gumbel density is not part of it."""
+        out = {}
+        for m in self.mechanisms():
+            x = obs[m.var]
+            if m.kind == "bernoulli":
+                l = m.module
+                t = (x * l - (l.clamp_min(0) + torch.log1p(torch.exp(-l.abs())))).sum(-1)
+            elif m.kind == "categorical":
+                t = (x * F.log_softmax(m.module, -1)).sum(-1)
+            elif m.kind == "spline":
+                u, extra = _unnormalize(x, m.normalize)
+                eps, log_det = m.module.inv_and_log_det(u)
+                t = (-0.5 * eps * eps - HALF_LOG_2PI - log_det + extra).sum(-1)
+            elif m.kind == "affine":
+                u, extra = _unnormalize(x, m.normalize)
+                loc, log_scale = m.module.params(torch.cat([obs[c] for c in m.ctx], 1))
+                eps = (u - loc) * torch.exp(-log_scale)
+                t = (-0.5 * eps * eps - HALF_LOG_2PI - log_scale + extra).sum(-1)
+            elif m.kind == "gumbel_max":
+                logits = m.module(torch.cat([obs[c] for c in m.ctx], 1))
+                t = F.log_softmax(logits, -1).gather(-1, x.to(torch.int64)).squeeze(-1)
+            else:
+                raise ValueError(f"unknown mechanism kind {m.kind!r}")
+            out[m.var] = t
+        return out
+
+    def nll(self, obs: Dict[str, Tensor]) -> Tensor:
+        """``sup_epoch``'s loss: -sum over variables and rows of ``log_prob``, divided by the batch size (TraceStorage_ELBO with an
+        empty guide averages identical deterministic particles)."""
+        terms = self.log_prob(obs)
+        B = next(iter(terms.values())).shape[0]
+        return -sum(t.sum() for t in terms.values()) / B
 
     def _abduct(self, obs: Dict[str, Tensor]) -> Dict[str, Tensor]:
         raise NotImplementedError
@@ -275,6 +361,12 @@ class FlowPGM(_BasePGM):
         self.bvol_flow = ConditionalAffine(DenseNN(2, widths, [1, 1], nn.LeakyReLU(0.1)))
         self.vvol_flow = ConditionalAffine(DenseNN(2, widths, [1, 1], nn.LeakyReLU(0.1)))
 
+    def mechanisms(self):
+        return [Mechanism("sex", "bernoulli", self.s_logit), Mechanism("mri_seq", "bernoulli", self.m_logit),
+                Mechanism("age", "spline", self.age_module[0]),
+                Mechanism("brain_volume", "affine", self.bvol_flow, ("sex", "age")),
+                Mechanism("ventricle_volume", "affine", self.vvol_flow, ("brain_volume", "age"))]
+
     def _abduct(self, obs):
         return {"age": self.age_module[0].inv(obs["age"]),
                 "brain_volume": self.bvol_flow.inv(obs["brain_volume"], torch.cat([obs["sex"], obs["age"]], 1)),
@@ -313,6 +405,11 @@ class MorphoMNISTPGM(_BasePGM):
         self.thickness_module = nn.ModuleList([LinearSpline(1, count_bins=4)])
         self.context_nn = ConditionalAffine(DenseNN(1, widths, [1, 1], nn.GELU()))
 
+    def mechanisms(self):
+        return [Mechanism("digit", "categorical", self.digit_logits),
+                Mechanism("thickness", "spline", self.thickness_module[0], (), True),
+                Mechanism("intensity", "affine", self.context_nn, ("thickness",), True)]
+
     def _abduct(self, obs):
         return {"thickness": self.thickness_module[0].inv(normalize_inv(obs["thickness"])),
                 "intensity": self.context_nn.inv(normalize_inv(obs["intensity"]), obs["thickness"])}
@@ -343,6 +440,9 @@ class ColourMNISTPGM(_BasePGM):
         super().__init__()
         self.digit_logits = nn.Parameter(torch.zeros(1, 10))   # uniform prior
         self.colour_logits = nn.Parameter(torch.zeros(1, 10))  # uniform prior
+
+    def mechanisms(self):
+        return [Mechanism("digit", "categorical", self.digit_logits), Mechanism("colour", "categorical", self.colour_logits)]
 
     def _abduct(self, obs):
         return {}
@@ -376,6 +476,11 @@ class ChestPGM(_BasePGM):
         self.race_logits = nn.Parameter(math.log(1 / 3) * torch.ones(1, 3))
         self.exact_gumbel_posterior = exact_gumbel_posterior
         self.generator: Optional[torch.Generator] = None  # set for reproducible Gumbel abduction (tests)
+
+    def mechanisms(self):
+        return [Mechanism("sex", "bernoulli", self.sex_logit), Mechanism("age", "spline", self.age_flow_components[0]),
+                Mechanism("race", "categorical", self.race_logits),
+                Mechanism("finding", "gumbel_max", self.finding_transform_GumbelMax.context_nn, ("age",))]
 
     def finding_logits(self, age: Tensor) -> Tensor:
         return self.finding_transform_GumbelMax.context_nn(age)

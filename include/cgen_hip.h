@@ -663,6 +663,63 @@ int cgen_rocauc(const float* scores, const float* labels, const int64_t* n_rows_
 int cgen_image_dist(int32_t n, int64_t elems_per_image, const float* a, const float* b, float* per_image, double* ws, double* acc,
                     cgen_stream_t);
 
+/* ------------------------------------------------------------------ parent SCM: log-likelihood and its parameter gradients (additive in ABI 411: new symbols and one new struct, nothing moved)
+ * train_pgm.py sup_epoch with --setup sup_pgm: -log p(parents) of flow_pgm.py's svi_model under an empty guide.  The SCM is a list
+ * of 1..CGEN_PGM_MAX_MECH scalar mechanisms, each scoring one variable of a row-major f32 table obs[rows][ncol] (a one-hot variable
+ * is its ncls columns, a class index is one column holding 0, 1, ...).  term[row][mech] = log p(variable | its parents):
+ *   BERNOULLI    x l - softplus(l)                                          p[0] = the logit [1]
+ *   CATEGORICAL  sum_j x_j log_softmax(l)_j                                 p[0] = the logits [ncls]
+ *   SPLINE       Normal(0,1) -> linear rational spline (pyro T.Spline(1, bins, bound, order="linear")): eps = spline^-1(u),
+ *                -eps^2/2 - log(2 pi)/2 - log|d spline / d eps|(eps); the identity outside +-bound.
+ *                p[0..3] = unnormalized widths [bins], heights [bins], derivatives [bins - 1], lambdas [bins]
+ *   AFFINE       (loc, log_scale) = MLP(ctx); eps = (u - loc) exp(-log_scale); -eps^2/2 - log(2 pi)/2 - log_scale
+ *   GUMBEL_MAX   log_softmax(MLP(ctx))[class]  (TransformedDistributionGumbelMax.log_prob: the base Gumbel density is not in it)
+ * `normalize` (SPLINE, AFFINE): the variable lives in [-1, 1] behind 2 sigmoid(.) - 1: u = logit((x + 1) / 2) with torch's
+ * SigmoidTransform clamp [FLT_MIN, 1 - FLT_EPSILON], and the term gets -(log 2 + logsigmoid(u) + logsigmoid(-u)); else u = x.
+ * MLP (pyro DenseNN): nctx (1..2) inputs -> width[0..nhidden) (nhidden 1..CGEN_PGM_MAX_HIDDEN, each <= CGEN_PGM_MAX_WIDTH) with
+ * `act` between -> 2 outputs (AFFINE) or ncls (GUMBEL_MAX); layer i has p[2 i] = weight [out][in] and p[2 i + 1] = bias [out].
+ * g[k] is where the gradient of p[k] goes (a slot of the caller's flat gradient buffer); the forward does not read g.
+ * Every buffer is f32 (sums and the spline algebra accumulate in f64 registers and round once).  Both entry points only enqueue on `stream`: no allocation, no host synchronisation, no host read of device
+ * data (capturable).  No atomics; every sum runs in a fixed order, so reruns give the same bits.  Arguments are checked before
+ * anything is launched and the error names the offending field. */
+#define CGEN_PGM_MAX_MECH 8
+#define CGEN_PGM_MAX_WIDTH 64
+#define CGEN_PGM_MAX_HIDDEN 3
+#define CGEN_PGM_MAX_BINS 8
+#define CGEN_PGM_MAX_CLS 16
+#define CGEN_PGM_ROWS 64 /* rows per workgroup: the workspace holds one row of partial sums per workgroup */
+enum cgen_pgm_kind { CGEN_PGM_BERNOULLI = 0, CGEN_PGM_CATEGORICAL = 1, CGEN_PGM_SPLINE = 2, CGEN_PGM_AFFINE = 3, CGEN_PGM_GUMBEL_MAX = 4 };
+enum cgen_pgm_act { CGEN_PGM_LEAKY_RELU = 0 /* slope 0.1 */, CGEN_PGM_GELU = 1 /* exact erf */, CGEN_PGM_SIGMOID = 2 };
+typedef struct cgen_pgm_mech {
+  int32_t kind;       /* cgen_pgm_kind */
+  int32_t normalize;  /* 0 / 1 (SPLINE, AFFINE) */
+  int32_t col;        /* first column of the variable in obs */
+  int32_t ncls;       /* CATEGORICAL, GUMBEL_MAX: 2..CGEN_PGM_MAX_CLS */
+  int32_t nctx;       /* AFFINE, GUMBEL_MAX: 1..2 */
+  int32_t ctx_col[2]; /* columns of the context, in the order the MLP takes them */
+  int32_t nhidden;
+  int32_t width[CGEN_PGM_MAX_HIDDEN];
+  int32_t act;        /* cgen_pgm_act */
+  int32_t bins;       /* SPLINE: 2..CGEN_PGM_MAX_BINS */
+  float bound;        /* SPLINE: > 0 */
+  const float* p[8];
+  float* g[8];
+} cgen_pgm_mech;
+/* bytes of workspace cgen_pgm_nll_fwd_bwd needs for `rows` rows: ceil(rows / CGEN_PGM_ROWS) rows of one partial sum per
+ * parameter-gradient slot (BERNOULLI 1, CATEGORICAL ncls, SPLINE 4 bins + 3, MLP its weights and biases).  A pure query. */
+int cgen_pgm_workspace(const cgen_pgm_mech* mechs, int32_t n, int32_t rows, int64_t* bytes);
+/* terms[rows][n] and loss_sum[0] = the sum of all terms (one workgroup, strided partial sums and a fixed tree).  Row r of the
+ * batch is obs row index[r] (device int64, optional; NULL = row r); an index outside [0, table_rows) makes that row's terms NaN. */
+int cgen_pgm_nll_fwd(const cgen_pgm_mech* mechs, int32_t n, const float* obs, int32_t ncol, int64_t table_rows, const int64_t* index,
+                     int32_t rows, float* terms, float* loss_sum, cgen_stream_t);
+/* the same forward, then g[k] of every mechanism = coef_dev[0] * d(sum of terms)/d(p[k]) (overwritten).  Two launches: one
+ * workgroup per (CGEN_PGM_ROWS rows, mechanism) writes its partial sums to a row of `workspace`; the second adds the rows in index
+ * order and applies the chain through softmax / softplus / sigmoid / cumsum of the root and spline parameters, which does not
+ * depend on the batch.  A parameter no row touches gets an exact 0. */
+int cgen_pgm_nll_fwd_bwd(const cgen_pgm_mech* mechs, int32_t n, const float* obs, int32_t ncol, int64_t table_rows, const int64_t* index,
+                         int32_t rows, float* terms, float* loss_sum, const float* coef_dev, float* workspace, int64_t workspace_bytes,
+                         cgen_stream_t);
+
 /* ------------------------------------------------------------------ step tail (K17; trainer.py:67-87, utils.py:178-225)
  * Flat-buffer fused global-norm -> clip -> skip predicate -> AdamW -> EMA.
  * state_dev: f32[8] = {sum_sq, grad_norm, clip_coef, skip_flag, n_skipped, opt_steps, n_skipped_nonfinite, -}.  LambdaLR warm-up, Adam
