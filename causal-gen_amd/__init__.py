@@ -5,9 +5,12 @@ model classes raise if the library or a GPU is missing."""
 __version__ = "0.1.0"
 
 
-def __getattr__(name):  # the data pipeline's classes, re-exported without importing torch at package import
-    if name in ("DeviceDataset", "DeviceLoader"):
+_LAZY = {"DeviceDataset": "data", "DeviceLoader": "data", "PgmCounterfactual": "pgm_cf", "DevicePGM": "pgm_cf"}
+
+
+def __getattr__(name):  # the data pipeline's and the device PGM's classes, re-exported without importing torch at package import
+    if name in _LAZY:
         import importlib
 
-        return getattr(importlib.import_module(__name__ + ".data"), name)
+        return getattr(importlib.import_module(__name__ + "." + _LAZY[name]), name)
     raise AttributeError(name)

@@ -118,9 +118,24 @@ class PgmMech(C.Structure):
                 ("bound", C.c_float), ("p", C.c_void_p * 8), ("g", C.c_void_p * 8)]
 
 
+class PgmPre(C.Structure):
+    """cgen_pgm_pre: one entry of the parents vector the HVAE takes (columns copied, or log-standardised as ukbb_preprocess does)."""
+    _fields_ = [("col", C.c_int32), ("width", C.c_int32), ("kind", C.c_int32), ("hi", C.c_float), ("lo", C.c_float), ("mu", C.c_float),
+                ("sd", C.c_float)]
+
+
+class PgmCfArgs(C.Structure):
+    """cgen_pgm_cf_args: observations, intervention values, mask, Gumbel-max uniforms and the outputs of cgen_pgm_counterfactual."""
+    _fields_ = [("obs", C.c_void_p), ("table_rows", C.c_int64), ("index", C.c_void_p), ("do_table", C.c_void_p), ("do_rows", C.c_int64),
+                ("do_index", C.c_void_p), ("do_mask_dev", C.c_void_p), ("uniforms", C.c_void_p * 8), ("cf", C.c_void_p), ("eps", C.c_void_p),
+                ("pa", C.c_void_p), ("cf_pa", C.c_void_p), ("ncol", C.c_int32), ("rows", C.c_int32), ("do_mask", C.c_uint32),
+                ("exact_gumbel", C.c_int32), ("npre", C.c_int32), ("reserved", C.c_int32), ("pre", PgmPre * 8)]
+
+
 PGM_BERNOULLI, PGM_CATEGORICAL, PGM_SPLINE, PGM_AFFINE, PGM_GUMBEL_MAX = 0, 1, 2, 3, 4
 PGM_LEAKY_RELU, PGM_GELU, PGM_SIGMOID = 0, 1, 2
 PGM_MAX_MECH, PGM_MAX_WIDTH, PGM_MAX_HIDDEN, PGM_MAX_BINS, PGM_MAX_CLS, PGM_ROWS = 8, 64, 3, 8, 16, 64
+PGM_MAX_PRE, PGM_PRE_COPY, PGM_PRE_LOGSTD = 8, 0, 1
 METRIC_BINARY, METRIC_CATEGORICAL, METRIC_CONTINUOUS = 0, 1, 2
 METRIC_NONE, METRIC_SIGMOID, METRIC_SOFTMAX, METRIC_TANH = 0, 1, 2, 3
 METRIC_N, METRIC_CORRECT, METRIC_ABS_ERR, METRIC_SKIPPED, METRIC_OVERFLOW = 0, 1, 2, 3, 4
@@ -221,6 +236,7 @@ PROTOTYPES = {
     "cgen_pgm_workspace": [C.POINTER(PgmMech), i32, i32, C.POINTER(i64)],
     "cgen_pgm_nll_fwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp],
     "cgen_pgm_nll_fwd_bwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp, vp, i64, vp],
+    "cgen_pgm_counterfactual": [C.POINTER(PgmMech), i32, C.POINTER(PgmCfArgs), vp],
     "cgen_metric_accum": [C.POINTER(MetricVar), i32, i32, vp],
     "cgen_rocauc": [vp, vp, vp, i64, i32, i64, vp, vp, vp],
     "cgen_image_dist": [i32, i64, vp, vp, vp, vp, vp, vp],

@@ -199,13 +199,15 @@ def gumbel_max_forward(gumbels: Tensor, logits: Tensor) -> Tensor:
     return (gumbels + logits).argmax(-1, keepdim=True)
 
 
-def gumbel_max_abduct(k: Tensor, logits: Tensor, generator: Optional[torch.Generator] = None) -> Tensor:
+def gumbel_max_abduct(k: Tensor, logits: Tensor, generator: Optional[torch.Generator] = None, u: Optional[Tensor] = None) -> Tensor:
     """ArgMaxGumbelMax.inv (layers.py:139-160), restated as is: a fresh standard Gumbel g_k for the observed class, whose noise
     becomes g_k - logit_k; every other class gets a Gumbel truncated below that value.  NOTE (reference behaviour, kept): the
     truncation level is g_k - logit_k while the winner's perturbed logit is g_k, so with log-probabilities (logit_k < 0) another
     class can still exceed the winner -- the reference therefore pins ``finding`` to its observed value unless it or its
-    parent is intervened on (flow_pgm.py:96-105).  `gumbel_max_abduct_exact` is the exact posterior."""
-    u = torch.rand(logits.shape, dtype=logits.dtype, device=logits.device, generator=generator)
+    parent is intervened on (flow_pgm.py:96-105).  `gumbel_max_abduct_exact` is the exact posterior.  `u`: the uniforms to use
+    (``logits``' shape) instead of a fresh draw, so that two evaluations can share their noise."""
+    if u is None:
+        u = torch.rand(logits.shape, dtype=logits.dtype, device=logits.device, generator=generator)
     gumbels = -(-(u.log())).log()
     mask = F.one_hot(k.squeeze(-1).to(torch.int64), num_classes=logits.shape[-1]).to(logits.dtype)
     top = (mask * gumbels).sum(-1, keepdim=True) - (mask * logits).sum(-1, keepdim=True)
@@ -214,11 +216,12 @@ def gumbel_max_abduct(k: Tensor, logits: Tensor, generator: Optional[torch.Gener
     return -torch.log(other * torch.exp(-g) + torch.exp(-top)) - other * logits
 
 
-def gumbel_max_abduct_exact(k: Tensor, logits: Tensor, generator: Optional[torch.Generator] = None) -> Tensor:
+def gumbel_max_abduct_exact(k: Tensor, logits: Tensor, generator: Optional[torch.Generator] = None, u: Optional[Tensor] = None) -> Tensor:
     """Exact Gumbel-max posterior (Maddison et al. 2014, top-down): the maximum Z ~ Gumbel(logsumexp(logits)) is attained by
     class k; every other perturbed logit is a Gumbel(logit_i) truncated at Z.  Returns the NOISE (perturbed logit - logit), so
-    gumbel_max_forward(result, logits) == k always."""
-    u = torch.rand(logits.shape, dtype=logits.dtype, device=logits.device, generator=generator)
+    gumbel_max_forward(result, logits) == k always.  `u`: the uniforms to use instead of a fresh draw."""
+    if u is None:
+        u = torch.rand(logits.shape, dtype=logits.dtype, device=logits.device, generator=generator)
     g = -(-(u.log())).log() + logits                      # independent Gumbel(logit_i)
     mask = F.one_hot(k.squeeze(-1).to(torch.int64), num_classes=logits.shape[-1]).to(logits.dtype)
     z = torch.logsumexp(logits, -1, keepdim=True) + (mask * (g - logits)).sum(-1, keepdim=True)   # the maximum (fresh Gumbel)

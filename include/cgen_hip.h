@@ -720,6 +720,69 @@ int cgen_pgm_nll_fwd_bwd(const cgen_pgm_mech* mechs, int32_t n, const float* obs
                          int32_t rows, float* terms, float* loss_sum, const float* coef_dev, float* workspace, int64_t workspace_bytes,
                          cgen_stream_t);
 
+/* ------------------------------------------------------------------ parent SCM: counterfactual parents (additive in ABI 411: one new symbol and two new structs, nothing moved)
+ * BasePGM.counterfactual (flow_pgm.py:71-108) followed by dscm.py's vae_preprocess: abduction -> action -> prediction over the same
+ * mechanism records, in ONE launch.  The records must be in topological order: every ctx_col[i] of a record must be the `col` of
+ * an EARLIER record (g[] is not read).  Row r of the batch is obs row index[r]; its intervention values are row do_index[r] of
+ * do_table, a table with the same column layout as obs.  A mechanism is TOUCHED if its bit is set in the mask or if any of its
+ * context mechanisms is touched.  In record order:
+ *   in the mask        its columns (ncls of them for CATEGORICAL) are the do row's columns, bit for bit
+ *   not touched        its columns are the observation's, bit for bit (the reference recomputes f(f^-1(obs)) here, which returns
+ *                      the observation up to rounding; the copy makes the null intervention exact)
+ *   touched AFFINE     eps = (u - loc(ctx_obs)) exp(-log_scale(ctx_obs)), u the un-normalised observation;
+ *                      cf = loc(ctx_cf) + exp(log_scale(ctx_cf)) eps, normalised again (2 sigmoid(.) - 1) when `normalize` is set;
+ *                      ctx_cf is read from the counterfactual values already produced for the row
+ *   touched GUMBEL_MAX noise from the observed class, the logits at ctx_obs and the caller's uniforms (exact_gumbel = 0:
+ *                      ArgMaxGumbelMax.inv of layers.py:139-160 as it is; 1: the exact top-down posterior), then the class is
+ *                      argmax(noise + logits(ctx_cf)), the first index winning ties; an observed class outside 0..ncls-1 gives NaN
+ * BERNOULLI, CATEGORICAL and SPLINE mechanisms have no context: they are only ever copied, and the spline inverse serves eps alone.
+ * Columns of the table that belong to no mechanism are copied through from the observation.
+ * Precision as above: buffers and activations f32; dot products, the spline algebra and the affine round trip (eps is not
+ * rounded between abduction and prediction) in f64 registers, rounded to f32 once.  No RNG, no atomics, no workspace: the launch
+ * is a pure function of its inputs and reruns give the same bits.  It only enqueues on the stream (capturable); arguments are
+ * checked before the launch and the error names the offending field.  cf, eps, pa and cf_pa must not overlap obs or do_table. */
+#define CGEN_PGM_MAX_PRE 8
+enum cgen_pgm_pre_kind { CGEN_PGM_PRE_COPY = 0, CGEN_PGM_PRE_LOGSTD = 1 };
+/* one entry of the parents vector the HVAE takes (vae_preprocess, in args.parents_x order) */
+typedef struct cgen_pgm_pre {
+  int32_t col;    /* first column of the variable in the table */
+  int32_t width;  /* columns taken (1, or the classes of a one-hot variable); col + width <= ncol */
+  int32_t kind;   /* COPY: the columns as they are.  LOGSTD (dscm.py ukbb_preprocess), per column:
+                     (log(max((x + 1) / 2 * (hi - lo) + lo, 1e-12)) - mu) / sd, evaluated in f64 */
+  float hi, lo;   /* LOGSTD: the variable's range behind the [-1, 1] normalisation */
+  float mu, sd;   /* LOGSTD: mean and standard deviation of its logarithm (sd != 0) */
+} cgen_pgm_pre;
+typedef struct cgen_pgm_cf_args {
+  const float* obs;            /* [table_rows][ncol] f32 observations */
+  int64_t table_rows;          /* >= 1; >= rows when index is NULL */
+  const int64_t* index;        /* device int64 [rows], optional: NULL = row r.  An index outside [0, table_rows) makes every output of that row NaN */
+  const float* do_table;       /* [do_rows][ncol] f32 intervention values, same column layout as obs; required when the host mask
+                                  is non-zero or do_mask_dev is given (only the columns of masked mechanisms are read) */
+  int64_t do_rows;             /* >= 1 with a do_table; >= rows when do_index is NULL */
+  const int64_t* do_index;     /* device int64 [rows], optional: NULL = row r of do_table.  With a non-zero mask, an index outside
+                                  [0, do_rows) makes every output of that row NaN */
+  const uint32_t* do_mask_dev; /* optional device word, read by the kernel INSTEAD of do_mask (a captured graph changes the
+                                  intervened variable between replays); bits at or above n are ignored */
+  const float* uniforms[CGEN_PGM_MAX_MECH]; /* uniforms[m]: [rows][ncls] f32 in [0, 1) for GUMBEL_MAX mechanism m (batch row r, not
+                                  index[r]), drawn by the caller; required for every GUMBEL_MAX record, not read for the others.
+                                  A uniform of exactly 0 is replaced by FLT_MIN (its Gumbel would be -inf) */
+  float* cf;                   /* [rows][ncol] the counterfactual table */
+  float* eps;                  /* optional [rows][n]: the abducted noise of every SPLINE and AFFINE mechanism, touched or not
+                                  (infer_exogeneous); 0 for roots and GUMBEL_MAX */
+  float* pa;                   /* optional [rows][ctx]: the factual parents as the HVAE takes them, ctx = sum of pre[].width */
+  float* cf_pa;                /* optional [rows][ctx]: the counterfactual parents, same layout (pa's bits under an empty mask) */
+  int32_t ncol;                /* columns of obs, do_table and cf */
+  int32_t rows;                /* 1..2^24 */
+  uint32_t do_mask;            /* bit m set: mechanism m is intervened on; a bit at or above n is an error */
+  int32_t exact_gumbel;        /* 0 / 1 */
+  int32_t npre;                /* 0..CGEN_PGM_MAX_PRE entries of pre[]; >= 1 when pa or cf_pa is given */
+  int32_t reserved;            /* 0 */
+  cgen_pgm_pre pre[CGEN_PGM_MAX_PRE];
+} cgen_pgm_cf_args;
+/* One workgroup per CGEN_PGM_ROWS rows walks the mechanisms in order, each MLP's weights staged in LDS once and evaluated at the
+ * factual and the counterfactual context of its rows.  Records and arguments travel by value in the kernel-argument segment. */
+int cgen_pgm_counterfactual(const cgen_pgm_mech* mechs, int32_t n, const cgen_pgm_cf_args* a, cgen_stream_t);
+
 /* ------------------------------------------------------------------ step tail (K17; trainer.py:67-87, utils.py:178-225)
  * Flat-buffer fused global-norm -> clip -> skip predicate -> AdamW -> EMA.
  * state_dev: f32[8] = {sum_sq, grad_norm, clip_coef, skip_flag, n_skipped, opt_steps, n_skipped_nonfinite, -}.  LambdaLR warm-up, Adam
