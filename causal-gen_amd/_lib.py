@@ -101,6 +101,16 @@ class LatentTailArgs(C.Structure):
                 ("coef", C.c_void_p), ("chan_scale", C.c_void_p)]
 
 
+class LatentTailFwdArgs(C.Structure):
+    """cgen_latent_tail_fwd_args: a decoder layer's forward latent tail (reparam + KL, z_proj, z_feat_proj) as one launch."""
+    _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("z_dim", C.c_int32), ("c", C.c_int32),
+                ("ctx", C.c_int32), ("kl_stride", C.c_int32), ("stream_id", C.c_uint32), ("logt", C.c_float),
+                ("h_in_rem", C.c_int64), ("h_out_rem", C.c_int64),
+                ("q_loc", View), ("q_ls", View), ("p_loc", View), ("p_ls", View), ("p_feat", View), ("h_in", View), ("pa", View),
+                ("eps", View), ("z", View), ("h_out", View), ("zf", View), ("img_p", C.c_void_p), ("img_f", C.c_void_p),
+                ("bias_p", C.c_void_p), ("bias_f", C.c_void_p), ("rng", C.c_void_p), ("kl_part", C.c_void_p)]
+
+
 class MetricVar(C.Structure):
     """cgen_metric_var: one variable of cgen_metric_accum (kind, transform, in-place prediction / target rows, the accumulator block)."""
     _fields_ = [("kind", C.c_int32), ("transform", C.c_int32), ("ncls", C.c_int32), ("reserved", C.c_int32), ("pred", C.c_void_p),
@@ -193,6 +203,8 @@ PROTOTYPES = {
                                   View, i32, i32, View, View, i32, vp],
     "cgen_latent_tail_bwd_supported": [C.POINTER(LatentTailArgs)],
     "cgen_latent_tail_bwd": [C.POINTER(LatentTailArgs), vp],
+    "cgen_latent_tail_fwd_supported": [C.POINTER(LatentTailFwdArgs)],
+    "cgen_latent_tail_fwd": [C.POINTER(LatentTailFwdArgs), vp],
     "cgen_kl_channel_sums": [i32, i32, i32, i32, i32, View, View, View, View, f32, vp, i32, vp],
     "cgen_elbo_finalize_fb": [i32, vp, i32, f32, vp, i32, f32, f32, f32, vp, vp, vp, vp],
     "cgen_im2col_strided": [i32, i32, i32, i32, i32, i32, i32, i32, i32, View, View, vp],
@@ -247,7 +259,7 @@ _RESTYPES = {"cgen_last_error": C.c_char_p}
 ABI_VERSION = 411  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
 _NOCHECK = {"cgen_version", "cgen_h16_format", "cgen_last_error", "cgen_conv2d_wgrad_plan", "cgen_reparam_kl_chunks", "cgen_like_chunks",
             "cgen_block3_supported", "cgen_block4_supported", "cgen_block4_pair_supported", "cgen_block3_pair_supported", "cgen_conv2d_pair_supported", "cgen_stem_conv_supported",
-            "cgen_predictor_supported", "cgen_predictor_tiled_supported", "cgen_batch_augment_arm", "cgen_latent_tail_bwd_supported"}
+            "cgen_predictor_supported", "cgen_predictor_tiled_supported", "cgen_batch_augment_arm", "cgen_latent_tail_bwd_supported", "cgen_latent_tail_fwd_supported"}
 
 
 class WgradBatchLaunch(C.Structure):

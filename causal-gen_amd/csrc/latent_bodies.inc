@@ -54,6 +54,31 @@ __device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
 __device__ __forceinline__ uint4 ld8(const View& v, int off) { return *(const uint4*)((const h16_t*)v.p + off); }
 __device__ __forceinline__ void st8(const View& v, int off, uint4 val) { *(uint4*)((h16_t*)v.p + off) = val; }
 
+// eight standard normals for the element group that starts at flat index i0 (a multiple of 8): two Philox groups
+__device__ __forceinline__ void reparam_eps8(const uint64_t seed, const uint64_t off, const uint32_t stream_id, const uint64_t i0, float (&eps)[8]) {
+  float n4[4];
+  Philox::normal4(seed, off, stream_id, i0 >> 2, n4);
+  eps[0] = n4[0]; eps[1] = n4[1]; eps[2] = n4[2]; eps[3] = n4[3];
+  Philox::normal4(seed, off, stream_id, (i0 >> 2) + 1, n4);
+  eps[4] = n4[0]; eps[5] = n4[1]; eps[6] = n4[2]; eps[7] = n4[3];
+}
+
+// z and the KL terms of 8 consecutive channels of one pixel, from values already in registers; returns the sum of the eight KL
+// terms (added in channel order).  Shared by the stand-alone kernel's item below and the fused forward latent tail
+// (latent_tail.hip), which feeds z on to its MFMAs.
+__device__ __forceinline__ float reparam_kl_fwd_vec8_math(const float logt, const float (&ql)[8], const float (&qs)[8], const float (&pl)[8],
+                                                          const float (&ps)[8], const float (&eps)[8], float (&z)[8]) {
+  float kl_acc = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float q = qs[k] + logt, pp = ps[k] + logt;
+    const float sq = expf(q), sp = expf(pp), d = ql[k] - pl[k];
+    z[k] = ql[k] + sq * eps[k];
+    kl_acc += -0.5f + pp - q + 0.5f * (sq * sq + d * d) / (sp * sp);
+  }
+  return kl_acc;
+}
+
 // one thread's share (8 consecutive channels of one pixel: element chunk * LAT_CHUNK + t * 8 ..) of sample b; returns its
 // KL contribution.  Shared by the stand-alone kernel (t = threadIdx.x of a 256-thread block) and the stage interpreter.
 __device__ __forceinline__ float reparam_kl_fwd_vec8_item(const LatP& p, const int b, const int chunk, const int t, const uint64_t seed, const uint64_t off) {
@@ -73,20 +98,9 @@ __device__ __forceinline__ float reparam_kl_fwd_vec8_item(const LatP& p, const i
     if (p.eps_in.p) {
       unpack8(ld8(p.eps_in, off8(p.eps_in, b, y, x, ch)), eps);
     } else {
-      const uint64_t i0 = (uint64_t)b * per + e;  // multiple of 8
-      float n4[4];
-      Philox::normal4(seed, off, p.stream_id, i0 >> 2, n4);
-      eps[0] = n4[0]; eps[1] = n4[1]; eps[2] = n4[2]; eps[3] = n4[3];
-      Philox::normal4(seed, off, p.stream_id, (i0 >> 2) + 1, n4);
-      eps[4] = n4[0]; eps[5] = n4[1]; eps[6] = n4[2]; eps[7] = n4[3];
+      reparam_eps8(seed, off, p.stream_id, (uint64_t)b * per + e, eps);  // (the index is a multiple of 8)
     }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float q = qs[k] + p.logt, pp = ps[k] + p.logt;
-      const float sq = expf(q), sp = expf(pp), d = ql[k] - pl[k];
-      z[k] = ql[k] + sq * eps[k];
-      kl_acc += -0.5f + pp - q + 0.5f * (sq * sq + d * d) / (sp * sp);
-    }
+    kl_acc = reparam_kl_fwd_vec8_math(p.logt, ql, qs, pl, ps, eps, z);
     st8(p.z, off8(p.z, b, y, x, ch), pack8(z));
     if (p.eps_out.p) st8(p.eps_out, off8(p.eps_out, b, y, x, ch), pack8(eps));
   }

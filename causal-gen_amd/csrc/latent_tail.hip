@@ -1,4 +1,5 @@
 // Backward latent tail of a stochastic decoder layer in ONE launch (binary16): include/cgen_hip.h, cgen_latent_tail_bwd.
+// (Its forward mirror image, cgen_latent_tail_fwd, is the second half of this file.)
 //
 // What it replaces ran as a strict chain of four launches per layer -- the two data gradients of z_feat_proj, the data gradient
 // of z_proj (accumulating into grad(z)) and the reparameterisation backward that reads grad(z) back, with the residual copy into
@@ -376,4 +377,355 @@ extern "C" int cgen_latent_tail_bwd(const cgen_latent_tail_bwd_args* a, cgen_str
 #undef LT_ORDER
 #undef LT_LAUNCH
   return check_launch("cgen_latent_tail_bwd");
+}
+
+// ============================================================================= forward latent tail (cgen_latent_tail_fwd)
+// What it replaces ran as three launches per layer: reparam_kl_fwd writes z, the 1x1 conv z_proj reads it back (with pa; bias + h +
+// p_feat in its epilogue), the 1x1 conv z_feat_proj reads it and p_feat again.  Here:
+//   * a tile is ONE KL chunk -- LAT_CHUNK / Z pixels of one sample, 256 threads with reparam_kl_fwd_vec8_item's thread -> element
+//     mapping -- so the KL partials keep their geometry and block_sum_256 its summation order;
+//   * z leaves as one 16-byte store per thread AND goes to an LDS tile, from which the MFMA pixel operand's z lanes are read; every
+//     other operand lane (pa / p_feat: 8 consecutive channels of one pixel) is a 16-byte global load straight into registers,
+//     requested together with the epilogue operands (h, p_feat) before the reparam math;
+//   * gridDim.y splits the output channels into LF_NP 32-channel blocks: rows [0, parts_p) own h' (K = [z | pa], one or two
+//     K-steps), the rest own zf (K = [z | p_feat]).  Every row recomputes z in registers from q_loc, q_ls and the same Philox
+//     counters; only row 0 reads p_loc / p_ls, stores z and the KL partial;
+//   * persistent over tiles: the row's weight slab goes to LDS once (rows permuted inside each 32-row block as in conv_px_kernel:
+//     a lane ends up with 8 consecutive output channels of its pixel, one 16-byte store per result);
+//   * ORDER 1 / 2: the summation order of conv_px_kernel / conv_smallp_kernel, whichever cgen_conv2d picks for the shape.
+namespace cgen {
+
+#define LF_NP 2     // 32-channel output blocks per workgroup
+#define LF_MAXKP 2  // K-steps of z_proj: Z + ceil8(ctx) <= 64
+#define LF_MAXKF 7  // K-steps of z_feat_proj: Z + C <= 208
+
+struct LfP {
+  int hw, per, chunks, ntiles, C, Cf, ctx8, parts_p;
+  int nks_p, nks_f, krow_p, krow_f;
+  int s_ql, s_qs, s_pl, s_ps, s_pf, s_eps, s_h, s_z, s_ho, s_zf, pa_sn, pa_sw;  // pixel strides (elements); pa: sample and pixel stride
+  const h16_t *q_loc, *q_ls, *p_loc, *p_ls, *p_feat, *eps, *h_in, *pa;
+  h16_t *z, *h_out, *zf;
+  const h16_t *img_p, *img_f;
+  const float *bias_p, *bias_f;
+  const uint64_t* rng;
+  uint32_t stream_id;
+  float logt;
+  float* kl_part;
+  int kl_stride;
+};
+
+// ROLE_P: this workgroup row computes h' (z_proj), else zf (z_feat_proj).  `part`: its index among the rows of its role.
+template <int ZD, int MAXK, int ORDER, bool ROLE_P>
+__device__ __forceinline__ void lf_run(const LfP& p, char* smem, const int part) {
+  constexpr int TP = LAT_CHUNK / ZD;  // pixels per tile
+  constexpr int NF = TP / 64;         // 16-pixel fragments per wave and tile: 2 (Z = 16) or 4 (Z = 8), taken two at a time
+  constexpr int CG = ZD / 8;          // 8-channel groups per pixel
+  constexpr int ZLD = ZD + 8;         // row of the z tile in LDS (elements)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
+  const int nks = ROLE_P ? p.nks_p : p.nks_f, K = nks * 32, ldw = K + 8;
+  const int krow = ROLE_P ? p.krow_p : p.krow_f, Co = ROLE_P ? p.C : p.Cf;
+  const int s1c = ROLE_P ? p.ctx8 : p.C;  // channels of the second input segment (pa is zero padded to ctx8)
+  const h16_t* img = ROLE_P ? p.img_p : p.img_f;
+  const float* bias = ROLE_P ? p.bias_p : p.bias_f;
+  h16_t* outp = ROLE_P ? p.h_out : p.zf;
+  const int s_out = ROLE_P ? p.s_ho : p.s_zf;
+  const int co_base = part * (LF_NP * 32), ch0 = co_base + fg * 8;
+  const bool first = ROLE_P && part == 0;  // the row that owns z and the KL partial
+  float* sm = (float*)smem;
+  char* zt = smem + 16;
+  char* wsl = zt + TP * ZLD * 2;
+  uint64_t seed = 0, off = 0;
+  if (!p.eps) { seed = p.rng[0]; off = p.rng[1]; }
+
+  uint4 ql, qs, pl, ps, ev, xb[2][MAXK], eh[ROLE_P ? 2 : 1][LF_NP], ep[ROLE_P ? 2 : 1][LF_NP];
+  int b = 0, chunk = 0, e0 = 0, gpx = 0, xb_b = 0, xb_chunk = 0, opx[2];
+  bool live = false, okf[2];
+  // the reparam operands of this thread's element group (8 channels of one pixel) of tile t
+  auto request_z = [&](int t) {
+    b = t / p.chunks; chunk = t - b * p.chunks;
+    e0 = chunk * LAT_CHUNK + tid * 8;
+    live = e0 < p.per;
+    gpx = b * p.hw + chunk * TP + (live ? tid / CG : 0);  // (a thread past the sample's end reads the tile's first pixel; nothing of it is kept)
+    const int ch = (tid % CG) * 8;
+    ql = *(const uint4*)(p.q_loc + (gpx * p.s_ql + ch)); qs = *(const uint4*)(p.q_ls + (gpx * p.s_qs + ch));
+    pl = lt_ld(p.p_loc, gpx * p.s_pl + ch, first); ps = lt_ld(p.p_ls, gpx * p.s_ps + ch, first);
+    ev = lt_ld(p.eps, gpx * p.s_eps + ch, p.eps != nullptr);
+  };
+  // the GEMM and epilogue operands of fragments 2 g and 2 g + 1 of this wave: pixel operand lane (fr, fg) of K-step i = channels
+  // i * 32 + fg * 8 .. + 8 of [z | segment 1] (each padded to 8, as cgen_conv2d concatenates) of the fragment's pixel fr
+  // (of tile (xb_b, xb_chunk): by then request_z may already have moved on to the next tile)
+  auto request_x = [&](int g) {
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      const int lp = xb_chunk * TP + (wave * NF + g * 2 + f) * 16 + fr;  // pixel inside the sample
+      okf[f] = lp < p.hw;
+      const int pc = okf[f] ? lp : xb_chunk * TP;
+      opx[f] = xb_b * p.hw + pc;
+#pragma unroll
+      for (int i = 0; i < MAXK; ++i) {
+        if (i < nks) {  // (uniform)
+          const int c = i * 32 + fg * 8 - ZD;
+          const bool s1 = c >= 0 && c < s1c;
+          if constexpr (ROLE_P) xb[f][i] = lt_ld(p.pa, xb_b * p.pa_sn + pc * p.pa_sw + c, s1);
+          else xb[f][i] = lt_ld(p.p_feat, opx[f] * p.s_pf + c, s1);
+        }
+      }
+      if constexpr (ROLE_P) {
+#pragma unroll
+        for (int pr = 0; pr < LF_NP; ++pr) {
+          const bool okc = ch0 + pr * 32 < Co;  // (Co is a multiple of 32: a block is inside or outside as a whole)
+          eh[f][pr] = lt_ld(p.h_in, opx[f] * p.s_h + ch0 + pr * 32, okc);
+          ep[f][pr] = lt_ld(p.p_feat, opx[f] * p.s_pf + ch0 + pr * 32, okc);
+        }
+      }
+    }
+  };
+  int t = (int)blockIdx.x;
+  request_z(t);
+  xb_b = b; xb_chunk = chunk;
+  request_x(0);
+  // ---- weight slab, once: LDS row pr * 32 + h * 16 + j holds output channel co_base + pr * 32 + (j >> 2) * 8 + h * 4 + (j & 3): MFMA h of
+  // block pr then leaves channels 8 fg + 4 h + {0..3} of the block in lane group fg
+  {
+    const int gpr = K >> 3;
+    for (int g = tid; g < LF_NP * 32 * gpr; g += 256) {
+      const int r = g / gpr, k = (g - r * gpr) * 8;
+      const int pr = r >> 5, h = (r >> 4) & 1, j = r & 15, c = co_base + pr * 32 + (j >> 2) * 8 + h * 4 + (j & 3);
+      *(uint4*)(wsl + (r * ldw + k) * 2) = lt_ld(img, c * krow + k, c < Co);
+    }
+  }
+  f32x4_t binit[LF_NP][2];  // the bias of this lane's channels: conv_px's initial accumulator value, conv_smallp's first epilogue term
+#pragma unroll
+  for (int pr = 0; pr < LF_NP; ++pr)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int co = ch0 + pr * 32 + h * 4;
+      const float4 bb = *(const float4*)((bias && co + 4 <= Co) ? (const void*)(bias + co) : (const void*)g_lt_zero);
+      binit[pr][h] = (f32x4_t){bb.x, bb.y, bb.z, bb.w};
+    }
+  const char* a_base = wsl + (fr * ldw + fg * 8) * 2;
+  for (;;) {
+    // ---- reparameterise: z to memory (row 0) and to the LDS tile, the KL partial of the chunk (row 0)
+    {
+      float fql[8], fqs[8], fpl[8], fps[8], fe[8], fz[8];
+      unpack8(ql, fql); unpack8(qs, fqs); unpack8(pl, fpl); unpack8(ps, fps);
+      if (p.eps) unpack8(ev, fe);
+      else reparam_eps8(seed, off, p.stream_id, (uint64_t)b * p.per + e0, fe);
+      float kl_acc = reparam_kl_fwd_vec8_math(p.logt, fql, fqs, fpl, fps, fe, fz);
+      if (!live) kl_acc = 0.f;
+      const uint4 zv = live ? pack8(fz) : make_uint4(0, 0, 0, 0);
+      *(uint4*)(zt + ((tid / CG) * ZLD + (tid % CG) * 8) * 2) = zv;
+      if (first) {
+        if (live) *(uint4*)(p.z + (gpx * p.s_z + (tid % CG) * 8)) = zv;
+        const float tot = block_sum_256(kl_acc, sm);  // (two barriers: the z tile is visible behind them)
+        if (tid == 0) p.kl_part[(int64_t)b * p.kl_stride + chunk] = tot;
+      } else {
+        __syncthreads();
+      }
+    }
+    // the next tile's reparam operands are requested now: they arrive under this tile's MFMAs and stores
+    t += (int)gridDim.x;
+    const bool more = t < p.ntiles;
+    if (more) request_z(t);
+#pragma unroll
+    for (int g = 0; g < NF / 2; ++g) {
+      if (g > 0) request_x(g);
+      if (fg < CG) {  // this lane's part of K-step 0 is z
+#pragma unroll
+        for (int f = 0; f < 2; ++f) xb[f][0] = *(const uint4*)(zt + (((wave * NF + g * 2 + f) * 16 + fr) * ZLD + fg * 8) * 2);
+      }
+      f32x4_t acc[LF_NP][2][2];  // [block][MFMA h][fragment]
+      if constexpr (ORDER == 1) {  // conv_px: the bias is the initial value, the K-steps accumulate in sequence
+#pragma unroll
+        for (int pr = 0; pr < LF_NP; ++pr)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) acc[pr][h][0] = acc[pr][h][1] = binit[pr][h];
+#pragma unroll
+        for (int i = 0; i < MAXK; ++i) {
+          if (i < nks) {  // (uniform)
+#pragma unroll
+            for (int pr = 0; pr < LF_NP; ++pr)
+#pragma unroll
+              for (int h = 0; h < 2; ++h) {
+                const h16x8 aq = *(const h16x8*)(a_base + ((pr * 32 + h * 16) * ldw) * 2 + i * 64);
+                acc[pr][h][0] = mfma_h16(aq, lt_frag(xb[0][i]), acc[pr][h][0], 0, 0, 0);
+                acc[pr][h][1] = mfma_h16(aq, lt_frag(xb[1][i]), acc[pr][h][1], 0, 0, 0);
+              }
+          }
+        }
+      } else {  // conv_smallp: K-step i belongs to wave i % 4's partial sum; the partials are added in wave order, then the bias
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          f32x4_t part_[LF_NP][2][2];
+#pragma unroll
+          for (int pr = 0; pr < LF_NP; ++pr)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) part_[pr][h][0] = part_[pr][h][1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int i = w; i < MAXK; i += 4) {
+            if (i < nks) {  // (uniform)
+#pragma unroll
+              for (int pr = 0; pr < LF_NP; ++pr)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                  const h16x8 aq = *(const h16x8*)(a_base + ((pr * 32 + h * 16) * ldw) * 2 + i * 64);
+                  part_[pr][h][0] = mfma_h16(aq, lt_frag(xb[0][i]), part_[pr][h][0], 0, 0, 0);
+                  part_[pr][h][1] = mfma_h16(aq, lt_frag(xb[1][i]), part_[pr][h][1], 0, 0, 0);
+                }
+            }
+          }
+#pragma unroll
+          for (int pr = 0; pr < LF_NP; ++pr)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+              for (int f = 0; f < 2; ++f) {
+                if (w == 0) acc[pr][h][f] = part_[pr][h][f];
+                else { acc[pr][h][f][0] += part_[pr][h][f][0]; acc[pr][h][f][1] += part_[pr][h][f][1]; acc[pr][h][f][2] += part_[pr][h][f][2]; acc[pr][h][f][3] += part_[pr][h][f][3]; }
+              }
+        }
+      }
+      // ---- epilogue straight from the accumulators, cgen_conv2d's order: (+ bias) + res1 (h) + res2 (p_feat), one rounding
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int pr = 0; pr < LF_NP; ++pr) {
+          if (!(okf[f] && ch0 + pr * 32 < Co)) continue;
+          float v[8], tp[8];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { v[e] = acc[pr][0][f][e]; v[4 + e] = acc[pr][1][f][e]; }
+          if (ORDER != 1 && bias) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[e] += binit[pr][0][e]; v[4 + e] += binit[pr][1][e]; }
+          }
+          if constexpr (ROLE_P) {
+            unpack8(eh[f][pr], tp);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += tp[e];
+            unpack8(ep[f][pr], tp);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += tp[e];
+          }
+          *(uint4*)(outp + (opx[f] * s_out + ch0 + pr * 32)) = pack8(v);
+        }
+    }
+    if (!more) break;
+    __syncthreads();  // every wave is done reading the z tile before the next one overwrites it
+    xb_b = b; xb_chunk = chunk;
+    request_x(0);
+  }
+}
+
+// ZD: latent channels; MAXKF: K-steps of z_feat_proj the instance is compiled for (the pixel fragments live in registers): 5 serves
+// C <= 128 at Z = 16 -- ukbb192's layers of 24x24 and above -- 7 the widest; ORDER as above.  The sequential order is the large
+// layers': three workgroups per CU (168 registers; at 128 it spills), which the grid below counts on -- at two per CU a 48x48 layer
+// was five serial round trips per workgroup, 30 us where the three launches' main chain took 27; the four-partial order (few
+// pixels, one round anyway) keeps its second accumulator set and two per CU.
+template <int ZD, int MAXKF, int ORDER>
+__global__ __launch_bounds__(256, ORDER == 1 ? 3 : 2) void latent_tail_fwd_kernel(LfP p) {
+  CGEN_SETPRIO();  // the chain's waves win issue arbitration over background weight-gradient waves on the same SIMD
+  extern __shared__ __attribute__((aligned(16))) char lf_smem[];
+  if ((int)blockIdx.y < p.parts_p) lf_run<ZD, LF_MAXKP, ORDER, true>(p, lf_smem, (int)blockIdx.y);
+  else lf_run<ZD, MAXKF, ORDER, false>(p, lf_smem, (int)blockIdx.y - p.parts_p);
+}
+
+static inline int lf_pad(int v, int m) { return (v + m - 1) / m * m; }
+static int lf_smallp_maxp() {
+  static const int v = [] { const char* e = getenv("CGEN_SMALLP_MAXP"); return e ? atoi(e) : 6000; }();
+  return v;
+}
+
+static const char* lf_reject(const cgen_latent_tail_fwd_args* a) {
+  if (!a) return "null args";
+  if (a->dtype != CGEN_F16) return "binary16 only";
+  if (a->n < 1 || a->h < 1 || a->w < 1) return "empty problem";
+  const int Z = a->z_dim, C = a->c;
+  if (Z != 8 && Z != 16) return "z_dim must be 8 or 16";
+  if (C < 32 || C % 32 != 0 || C > 192) return "C must be a multiple of 32, at most 192";
+  const int Cf = a->zf.p ? a->zf.c : 0;
+  if (a->zf.p && (Cf < 32 || Cf % 32 != 0 || Cf > 192)) return "zf.c must be a multiple of 32, at most 192";
+  if (a->ctx < 1 || Z + lf_pad(a->ctx, 8) > 32 * LF_MAXKP) return "z_proj's K is more than two K-steps";
+  if (a->h_in_rem || a->h_out_rem) return "remainder planes are not served";
+  const int64_t P = (int64_t)a->n * a->h * a->w;
+  if (P >= (1ll << 31) / 2) return "too many pixels";
+  // which kernel cgen_conv2d serves the two convs with must be the same for both and known from the shape alone
+  if ((a->h < 5 || a->w < 5) && P > lf_smallp_maxp()) return "an image side below 5 with more pixels than the small-image conv takes";
+  if (getenv("CGEN_CONV_NO_PX") || getenv("CGEN_CONV_NO_SMALLP") || getenv("CGEN_CONV_GENERIC") || getenv("CGEN_PX_MODE") ||
+      getenv("CGEN_SMALLP_MAXP_LONGK") || getenv("CGEN_SMALLP_LONGK"))
+    return "a conv dispatch knob is set";
+  struct { const cgen_view* v; int c; bool need; } vs[] = {
+      {&a->q_loc, Z, true}, {&a->q_ls, Z, true}, {&a->p_loc, Z, true}, {&a->p_ls, Z, true}, {&a->p_feat, C, true}, {&a->h_in, C, true},
+      {&a->eps, Z, false},  {&a->z, Z, true},    {&a->h_out, C, true}, {&a->zf, Cf, false}};
+  for (auto& e : vs) {
+    const cgen_view& v = *e.v;
+    if (!v.p) {
+      if (e.need) return "a required view is absent";
+      continue;
+    }
+    if (v.c != e.c) return "a view has the wrong channel count";
+    if (!vec16_ok(v, 2)) return "a view is not 16-byte clean";
+    if (v.sw < v.c) return "pixel stride below the channel count";
+    if (v.sh != (int64_t)a->w * v.sw || v.sn != (int64_t)a->h * v.sh) return "a view is not linear in pixels";
+    if ((P * v.sw + v.c) * 2 >= (1ll << 31)) return "a view spans 2^31 bytes or more";
+  }
+  {
+    const cgen_view& v = a->pa;
+    const int c8 = lf_pad(a->ctx, 8);
+    if (!v.p || v.c != a->ctx) return "pa is absent or has the wrong channel count";
+    if (!vec16_ok(v, 2)) return "pa is not 16-byte clean";
+    if (a->ctx % 8 != 0 && v.cpad < c8) return "pa is not zero padded to 8 channels";
+    const bool constant = v.sh == 0 && v.sw == 0, linear = v.sw >= c8 && v.sh == (int64_t)a->w * v.sw && v.sn == (int64_t)a->h * v.sh;
+    if (!constant && !linear) return "pa is neither spatially constant nor linear in pixels";
+    if (v.sn < 0 || ((int64_t)a->n * v.sn + P * v.sw + c8) * 2 >= (1ll << 31)) return "pa spans 2^31 bytes or more";
+  }
+  if (!a->img_p || (a->zf.p && !a->img_f)) return "a weight image is absent";
+  if (((uintptr_t)a->img_p | (uintptr_t)a->img_f | (uintptr_t)a->bias_p | (uintptr_t)a->bias_f) % 16) return "a weight image or bias is not 16-byte aligned";
+  if (!a->eps.p && !a->rng) return "neither eps nor rng";
+  if (!a->kl_part || a->kl_stride < ceil_div((int64_t)a->h * a->w * Z, LAT_CHUNK)) return "kl_part absent or kl_stride below the chunk count";
+  return nullptr;
+}
+
+}  // namespace cgen
+
+extern "C" int cgen_latent_tail_fwd_supported(const cgen_latent_tail_fwd_args* a) { return cgen::lf_reject(a) == nullptr ? 1 : 0; }
+
+extern "C" int cgen_latent_tail_fwd(const cgen_latent_tail_fwd_args* a, cgen_stream_t stream) {
+  using namespace cgen;
+  if (const char* why = lf_reject(a)) return fail(CGEN_EUNSUPPORTED, "cgen_latent_tail_fwd: %s", why);
+  LfP p;
+  memset(&p, 0, sizeof(p));
+  const int Z = a->z_dim, P = a->n * a->h * a->w;
+  p.hw = a->h * a->w; p.per = p.hw * Z; p.chunks = ceil_div(p.per, LAT_CHUNK); p.ntiles = a->n * p.chunks;
+  p.C = a->c; p.Cf = a->zf.p ? a->zf.c : 0; p.ctx8 = lf_pad(a->ctx, 8);
+  p.nks_p = ceil_div(Z + p.ctx8, 32); p.nks_f = p.Cf ? ceil_div(Z + p.C, 32) : 0;
+  p.krow_p = lf_pad(Z + p.ctx8, 32) + 32; p.krow_f = lf_pad(Z + p.C, 32) + 32;
+  p.parts_p = ceil_div(p.C / 32, LF_NP);
+  const int parts = p.parts_p + ceil_div(p.Cf / 32, LF_NP);
+  p.s_ql = (int)a->q_loc.sw; p.s_qs = (int)a->q_ls.sw; p.s_pl = (int)a->p_loc.sw; p.s_ps = (int)a->p_ls.sw; p.s_pf = (int)a->p_feat.sw;
+  p.s_eps = (int)a->eps.sw; p.s_h = (int)a->h_in.sw; p.s_z = (int)a->z.sw; p.s_ho = (int)a->h_out.sw; p.s_zf = (int)a->zf.sw;
+  p.pa_sn = (int)a->pa.sn; p.pa_sw = (int)a->pa.sw;
+  p.q_loc = (const h16_t*)a->q_loc.p; p.q_ls = (const h16_t*)a->q_ls.p; p.p_loc = (const h16_t*)a->p_loc.p; p.p_ls = (const h16_t*)a->p_ls.p;
+  p.p_feat = (const h16_t*)a->p_feat.p; p.eps = (const h16_t*)a->eps.p; p.h_in = (const h16_t*)a->h_in.p; p.pa = (const h16_t*)a->pa.p;
+  p.z = (h16_t*)a->z.p; p.h_out = (h16_t*)a->h_out.p; p.zf = (h16_t*)a->zf.p;
+  p.img_p = (const h16_t*)a->img_p; p.img_f = (const h16_t*)a->img_f; p.bias_p = a->bias_p; p.bias_f = a->bias_f;
+  p.rng = a->rng; p.stream_id = a->stream_id; p.logt = a->logt; p.kl_part = a->kl_part; p.kl_stride = a->kl_stride;
+  // LDS: 16 bytes for the block sum, the z tile [LAT_CHUNK / Z][Z + 8], the larger of the two roles' slabs [32 LF_NP][K + 8]: at most 38 KiB
+  const int kmax = (p.nks_p > p.nks_f ? p.nks_p : p.nks_f) * 32;
+  const size_t lds = 16 + (size_t)(LAT_CHUNK / Z) * (Z + 8) * 2 + (size_t)LF_NP * 32 * (kmax + 8) * 2;
+  // the order cgen_conv2d sums in at this shape (launch_conv): conv_smallp_kernel takes few pixels and sides below 5 (which lf_reject
+  // admits only with few pixels), conv_px_kernel every other 1x1 conv with a short K
+  const int order = (P <= lf_smallp_maxp() || a->h < 5 || a->w < 5) ? 2 : 1;
+  // persistent over tiles: as many workgroups as are resident at once (three or two per CU, 256 CUs), every one the same number of tiles
+  const int resident = (order == 1 ? 768 : 512) / parts;  // (parts <= 6)
+  const int rounds = (p.ntiles + resident - 1) / resident;
+  const int gx = (p.ntiles + rounds - 1) / rounds;
+  const dim3 grid(gx, parts), block(256);
+  const bool small = p.nks_f <= 5;
+#define LF_LAUNCH(Z_, KF_, ORD_) hipLaunchKernelGGL((latent_tail_fwd_kernel<Z_, KF_, ORD_>), grid, block, lds, (hipStream_t)stream, p)
+#define LF_ORDER(Z_, KF_) do { if (order == 1) LF_LAUNCH(Z_, KF_, 1); else LF_LAUNCH(Z_, KF_, 2); } while (0)
+  if (Z == 16) { if (small) LF_ORDER(16, 5); else LF_ORDER(16, LF_MAXKF); }
+  else { if (small) LF_ORDER(8, 5); else LF_ORDER(8, LF_MAXKF); }
+#undef LF_ORDER
+#undef LF_LAUNCH
+  return check_launch("cgen_latent_tail_fwd");
 }

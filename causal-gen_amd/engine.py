@@ -337,6 +337,11 @@ class Engine(WgradMixin):
         # grad(z) / grad(p_feat)); 1: one f32 sum and one rounding per output -- closer to exact, and no longer the same bits
         self.lat_tail_exact = os.environ.get("CGEN_LAT_TAIL_EXACT", "0") != "0"
         self.lat_tails = 0  # fused launches of the last backward()
+        # The same layer's FORWARD tail -- reparam + KL, z_proj, z_feat_proj -- as one launch (cgen_latent_tail_fwd; latent_tail_fwd below):
+        # the three launches' bits, the three tape entries.  0: the three launches.
+        self.lat_tail_fwd = os.environ.get("CGEN_LAT_TAIL_FWD", "1") != "0"
+        self.lat_tail_fwd_minpx = int(os.environ.get("CGEN_LAT_TAIL_FWD_MINPX", "0"))  # layers with fewer pixels (n * h * w) keep the three launches
+        self.lat_tails_fwd = 0  # fused forward launches since begin()
         self.wgrad_bg_wgs = int(os.environ.get("CGEN_WGRAD_BG_WGS", "304"))
         self.wgrad_bg_reduce = os.environ.get("CGEN_WGRAD_BG_REDUCE", "1") != "0"
         self._wg_cum, self._wg_total, self._wg_nflush = 0.0, 0.0, 0
@@ -435,6 +440,7 @@ class Engine(WgradMixin):
         self._wg_forked = False
         self._split_done = False
         self.passes = 0
+        self.lat_tails_fwd = 0
         self.stream = torch.cuda.current_stream(self.device).cuda_stream
 
     def new(self, n, h, w, c, rg=True, es=None, rem=False):
@@ -1132,6 +1138,56 @@ class Engine(WgradMixin):
         if self.recording:
             self.tape.append((self._bw_reparam, (q_loc, q_ls, p_loc, p_ls, z, logt, None if fb is None else fb[2], self.kl_coef_override)))
         return z
+
+    def latent_tail_fwd(self, site_p, site_f, q_loc, q_ls, p_loc, p_ls, p_feat, h, pa, eps, stream_id, logt, kl_ptr, kl_stride, fb=None,
+                        tape_hold=None):
+        """reparam_kl -> conv(z_proj, [z, pa], res1=h, res2=p_feat, trunk=True) -> conv(z_feat_proj, [z, p_feat]) (`site_f` None: the
+        layer has none) as ONE launch on the current stream, with the three launches' bits and their three tape entries in their
+        places (z_feat_proj's goes to `tape_hold`).  Returns (z, h', zf or None), or None -- nothing done, the caller runs the three
+        launches -- when the kernel does not serve the layer, when per-site timing is on, or under CGEN_ABLATE."""
+        if not self.lat_tail_fwd or self.dt != F16 or self.prof is not None or self._ablate:
+            return None
+        n, hh, ww, zd, c = q_loc.n, q_loc.h, q_loc.w, q_loc.c, site_p.co
+        if n * hh * ww < self.lat_tail_fwd_minpx or h.rem or p_feat.rem or (self.trunk_rem and max(hh, ww) <= self.trunk_maxres):
+            return None
+        if site_p.ks != 1 or list(site_p.seg_c) != [zd, pa.c] or (site_f is not None and (site_f.ks != 1 or list(site_f.seg_c) != [zd, c])):
+            return None
+        t = _lib.LatentTailFwdArgs()
+        t.dtype, t.n, t.h, t.w, t.z_dim, t.c, t.ctx = self.dt, n, hh, ww, zd, c, pa.c
+        t.kl_stride, t.stream_id, t.logt = kl_stride, stream_id, logt
+        t.q_loc, t.q_ls, t.p_loc, t.p_ls, t.p_feat, t.h_in, t.pa = q_loc.cv(), q_ls.cv(), p_loc.cv(), p_ls.cv(), p_feat.cv(), h.cv(), pa.cv()
+        t.eps = eps.cv() if eps is not None else NULL_VIEW
+        # (probe views for _supported(), which looks at shapes, strides and alignment: the layout new() will give the outputs, at a
+        # pointer with the arena's alignment)
+        probe = lambda c_: View(h.base.ptr, hh * ww * c_, ww * c_, c_, c_, 0)
+        t.z, t.h_out, t.zf = probe(zd), probe(c), (NULL_VIEW if site_f is None else probe(site_f.co))
+        t.img_p, t.img_f = site_p.img_fwd, (site_f.img_fwd if site_f is not None else None)
+        bp, bf = site_p.conv.bias, (site_f.conv.bias if site_f is not None else None)
+        t.bias_p, t.bias_f = (bp.data_ptr() if bp is not None else None), (bf.data_ptr() if bf is not None else None)
+        t.rng, t.kl_part = self.rng_ptr(), kl_ptr
+        if not self.lib.latent_tail_fwd_supported(C.byref(t)):
+            return None
+        # ---- committed: the allocations, the launches' bookkeeping and the tape entries of the three calls, in their order
+        z = self.new(n, hh, ww, zd)
+        if fb is not None:
+            self.lib.kl_channel_sums(self.dt, n, hh, ww, zd, q_loc.cv(), q_ls.cv(), p_loc.cv(), p_ls.cv(), logt, fb[0] + 4 * fb[2], fb[1], self.stream)
+            self.launches += 1
+        h2 = self.new(n, hh, ww, c)
+        zf = self.new(n, hh, ww, site_f.co) if site_f is not None else None
+        t.z, t.h_out, t.zf = z.cv(), h2.cv(), (zf.cv() if zf is not None else NULL_VIEW)
+        self.lib.latent_tail_fwd(C.byref(t), self.stream)
+        self.launches += 1
+        self.lat_tails_fwd += 1
+        if self.recording:
+            self.tape.append((self._bw_reparam, (q_loc, q_ls, p_loc, p_ls, z, logt, None if fb is None else fb[2], self.kl_coef_override)))
+            if self._dbg_names is not None:
+                self._dbg_names[id(h2.base)] = site_p.name
+            self.tape.append((self._bw_conv, (site_p, [z, pa], ACT_NONE, h2, h, p_feat), self._bw_tag))
+            if zf is not None:
+                if self._dbg_names is not None:
+                    self._dbg_names[id(zf.base)] = site_f.name
+                (self.tape if tape_hold is None else tape_hold).append((self._bw_conv, (site_f, [z, p_feat], ACT_NONE, zf, None, None), 0))
+        return z, h2, zf
 
     def sample_gaussian(self, loc, ls, eps, stream_id, logt):
         z = self.new(loc.n, loc.h, loc.w, loc.c)

@@ -744,6 +744,9 @@ class HVAE(nn.Module):
                 eng.tape[t_q0:] = eng.tape[t_q1:] + eng.tape[t_q0:t_q1]
             zd = blk.z_dim
             p_loc, p_ls, p_feat = pout.chan(0, zd), pout.chan(zd, 2 * zd), pout.chan(2 * zd, pout.c)
+            feat = not blk.q_correction and i + 1 < len(dec.blocks)
+            hold = []
+            tail = None  # (z, h', zf) when the layer's forward tail ran as one launch (Engine.latent_tail_fwd)
             if blk.stochastic:
                 sid += 1
                 if acts is not None:
@@ -757,7 +760,11 @@ class HVAE(nn.Module):
                     kptr = kl[0] + 4 * kl[2][i] if kl is not None else self._scratch_kl(eng, B, res, zd)
                     kstride = kl[1] if kl is not None else _lib.load().reparam_kl_chunks(res, res, zd)
                     fbl = None if fb is None else (fb[0], fb[1], fb[2][i])
-                    z = eng.reparam_kl(q_loc, q_ls, p_loc, p_ls, eps, sid, logt, kptr, kstride, fb=fbl)
+                    # reparam + KL, z_proj and z_feat_proj as ONE launch on the main stream where the kernel serves the layer: the same
+                    # bits, the same three tape entries (z_feat_proj's in `hold`)
+                    tail = eng.latent_tail_fwd(self._site(eng, blk.z_proj), self._site(eng, blk.z_feat_proj) if feat else None, q_loc, q_ls,
+                                               p_loc, p_ls, p_feat, h, pa, eps, sid, logt, kptr, kstride, fb=fbl, tape_hold=hold)
+                    z = tail[0] if tail is not None else eng.reparam_kl(q_loc, q_ls, p_loc, p_ls, eps, sid, logt, kptr, kstride, fb=fbl)
                     if collect == "z":
                         out.append(z)
                     elif collect == "q":
@@ -776,12 +783,24 @@ class HVAE(nn.Module):
             else:
                 z = p_loc
             z_cur = z
-            feat = not blk.q_correction and i + 1 < len(dec.blocks)
-            hold = []
             # the next layer's prior chain (z_feat_proj -> prior Block) on the side stream, forked HERE but enqueued behind z_proj:
             # the main chain must be the first edge out of the fork for a captured graph to keep it on one queue (Engine.fork_mark)
             ahead = feat and pipeline and two and dec.blocks[i + 1].stochastic and not dec.blocks[i + 1].q_correction
             mark = eng.fork_mark() if ahead and eng.fwd_mainfirst else None
+            if tail is not None:
+                # the one launch is done, on the main stream: the fork for the next layer's prior chain (upsample -> prior Block) sits
+                # behind it, and the conv Block -- the main chain -- is still the first edge out of it
+                h = tail[1]
+                t_zp = len(eng.tape)
+                if ahead and mark is None and eng.fork_side():
+                    side_ahead = True
+                h = self._run_block(eng, blk.conv, [h])
+                if mark is not None and eng.fork_side(after=mark):
+                    side_ahead = True
+                if feat:
+                    z = tail[2]
+                eng.tape[t_zp:t_zp] = hold
+                continue
             if ahead and mark is None and eng.fork_side():
                 z = eng.on_side(lambda: eng.conv(self._site(eng, blk.z_feat_proj), [z_cur, p_feat], ACT_NONE, tape_hold=hold))
                 side_ahead = True

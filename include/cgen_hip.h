@@ -432,6 +432,43 @@ typedef struct cgen_latent_tail_bwd_args {
 int cgen_latent_tail_bwd_supported(const cgen_latent_tail_bwd_args* a);
 int cgen_latent_tail_bwd(const cgen_latent_tail_bwd_args* a, cgen_stream_t stream);
 
+/* ------------------------------------------------------------------ forward latent tail of a decoder layer (additive in ABI 411: new symbols only)
+ * One launch (csrc/latent_tail.hip; binary16) for what follows a stochastic decoder layer's prior and posterior Blocks in the
+ * forward pass (vae.py:263-300): the reparameterisation + KL and the two 1x1 convs that read z.
+ *   z       = rn16(q_loc + exp(q_ls + logt) * eps)                eps: the view, or Philox(rng, stream_id, b * h*w*Z + e) when absent
+ *   kl_part[b * kl_stride + chunk]                                cgen_reparam_kl_fwd's partials: same chunks, same summation order
+ *   h_out   = rn16(bias_p + W_p [z | pa] + h_in + p_feat)         z_proj: cgen_conv2d with res1 = h_in, res2 = p_feat
+ *   zf      = rn16(bias_f + W_f [z | p_feat])                     z_feat_proj; zf.p == NULL: the layer has none
+ * z, kl_part, h_out and zf are bit for bit what cgen_reparam_kl_fwd + cgen_conv2d x 2 leave: every GEMM is summed in the order of
+ * the kernel cgen_conv2d picks for the shape (conv_px: bias as the initial value, K-steps in sequence; conv_smallp, few pixels:
+ * K-step i in partial i % 4, the partials added in wave order, then the bias).
+ * Weights: the forward images cgen_weight_prep (mode 0) writes for the two convs -- img_p: C rows x (ceil32(Z + ceil8(ctx)) + 32),
+ * img_f: zf.c rows x (ceil32(Z + C) + 32); biases f32, optional.  pa is [n,h,w,ctx], linear in pixels or spatially constant (sh == sw == 0),
+ * zero padded to a multiple of 8 channels (cpad).
+ * Served (cgen_latent_tail_fwd_supported() == 1, answered without a GPU): CGEN_F16; Z in {8, 16}; C and zf.c multiples of 32 up to
+ * 192; Z + ceil8(ctx) <= 64; no remainder planes (h_in_rem == h_out_rem == 0); every view 16-byte aligned, linear in pixels
+ * (sn == h * sh, sh == w * sw; pa as above) and below 2^31 bytes; an image side below 5 only up to the small-image conv's pixel limit.
+ * Anything else: _supported() == 0 and cgen_latent_tail_fwd returns CGEN_EUNSUPPORTED without launching. */
+typedef struct cgen_latent_tail_fwd_args {
+  int32_t dtype, n, h, w, z_dim, c;     /* c: channels of h_in, h_out and p_feat */
+  int32_t ctx;                          /* channels of pa */
+  int32_t kl_stride;
+  uint32_t stream_id;
+  float logt;
+  int64_t h_in_rem, h_out_rem;          /* remainder planes of the f16 trunk (cgen_conv_args): not served, must be 0 */
+  cgen_view q_loc, q_ls, p_loc, p_ls;   /* [n,h,w,Z] each */
+  cgen_view p_feat, h_in;               /* [n,h,w,C] */
+  cgen_view pa;                         /* [n,h,w,ctx] */
+  cgen_view eps;                        /* [n,h,w,Z] or absent */
+  cgen_view z, h_out, zf;               /* outputs: [n,h,w,Z], [n,h,w,C], [n,h,w,zf.c] or absent */
+  const void *img_p, *img_f;
+  const float *bias_p, *bias_f;
+  const uint64_t* rng;                  /* device {seed, offset}, as in cgen_reparam_kl_fwd; needed without eps */
+  float* kl_part;
+} cgen_latent_tail_fwd_args;
+int cgen_latent_tail_fwd_supported(const cgen_latent_tail_fwd_args* a);
+int cgen_latent_tail_fwd(const cgen_latent_tail_fwd_args* a, cgen_stream_t stream);
+
 /* ------------------------------------------------------------------ likelihoods (K11-K14) and ELBO
  * Discretised Gaussian (vae.py:352-411).  params view holds [loc(C) | logscale(C) | coeff(3, only C==3)] per pixel
  * (the raw 1x1-conv outputs); x is NHWC.  For C == 3 a params view of >= 9 channels selects vae.py's autoregressive
