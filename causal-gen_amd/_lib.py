@@ -64,6 +64,14 @@ class WredDesc(C.Structure):
                 ("numel", C.c_int64)]
 
 
+class WredItem(C.Structure):
+    """cgen_wred_item: one workgroup of cgen_wgrad_reduce_tiles (a tile of a site's partials, or a run of its bias gradient)."""
+    _fields_ = [("partial", C.c_void_p), ("grad", C.c_void_p), ("kind", C.c_int32), ("nsplit", C.c_int32),
+                ("split_stride", C.c_int32), ("vec", C.c_int32), ("v4", C.c_int32), ("accumulate", C.c_int32),
+                ("unscale", C.c_float), ("taps", C.c_int32), ("inner", C.c_int32), ("ci_total", C.c_int32), ("layout", C.c_int32),
+                ("a0", C.c_int32), ("na", C.c_int32), ("b0", C.c_int32), ("nb", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AdamwArgs(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p),
                 ("count", C.c_int64), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
@@ -179,6 +187,9 @@ PROTOTYPES = {
     "cgen_conv2d_wgrad": [C.POINTER(WgradArgs), vp],
     "cgen_weight_prep": [vp, vp, vp, i32, vp],
     "cgen_wgrad_reduce": [vp, vp, vp, i32, vp],
+    "cgen_weight_prep_ref": [vp, vp, vp, i32, vp],
+    "cgen_wgrad_reduce_tiles": [vp, i32, vp],
+    "cgen_wgrad_reduce_ref": [vp, vp, vp, i32, vp],
     "cgen_avgpool_fwd": [i32, i32, i32, i32, i32, View, View, vp],
     "cgen_avgpool_bwd": [i32, i32, i32, i32, i32, View, View, i32, vp],
     "cgen_adaptive_avgpool_fwd": [i32, i32, i32, i32, i32, i32, View, View, vp],

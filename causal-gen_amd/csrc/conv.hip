@@ -3232,3 +3232,14 @@ extern "C" int cgen_wgrad_reduce(const cgen_wred_desc* descs, const int32_t* csi
   hipLaunchKernelGGL(wred_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, descs, csite, cidx);
   return check_launch("cgen_wgrad_reduce");
 }
+
+// The tiled forms live in csrc/multitensor.hip; these names keep the per-element kernels above reachable as the reference.
+extern "C" int cgen_weight_prep_ref(const cgen_wprep_desc* descs, const int32_t* csite, const int32_t* cidx, int32_t nchunks,
+                                    cgen_stream_t stream) {
+  return cgen_weight_prep(descs, csite, cidx, nchunks, stream);
+}
+
+extern "C" int cgen_wgrad_reduce_ref(const cgen_wred_desc* descs, const int32_t* csite, const int32_t* cidx, int32_t nchunks,
+                                     cgen_stream_t stream) {
+  return cgen_wgrad_reduce(descs, csite, cidx, nchunks, stream);
+}

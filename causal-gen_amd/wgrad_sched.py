@@ -12,6 +12,61 @@ import torch
 from . import _lib
 
 
+WRED_TILE, WRED_TILE_DEEP = 2048, 1024  # elements of a cgen_wgrad_reduce_tiles workgroup (WRED_T, WRED_T_DEEP of csrc/multitensor.hip)
+_WRED_REF = os.environ.get("CGEN_WRED_REF", "0") == "1"  # A/B: reduce with the per-element reference kernel
+
+
+def _even_cut(n, most):
+    """Width (a multiple of 4 where that is possible) of the fewest equal cuts of n columns that are at most `most` wide."""
+    if n <= most:
+        return n
+    most = max(most - most % 4, 1) if most >= 4 else most
+    cuts = -(-n // most)
+    w = -(-n // cuts)
+    return min(most, -(-w // 4) * 4 if most >= 4 else w)
+
+
+def plan_wred_items(descs):
+    """The workgroup table of cgen_wgrad_reduce_tiles for a list of WredDesc: every site cut into tiles of whole partial rows whose
+    sums leave as runs of the OIHW gradient (>= 128 bytes wherever the site is that large), the bias gradients as items of their
+    own.  The longest split chains go first, so they are not what the launch ends on."""
+    items = []
+    for d in descs:
+        taps, co, ci = d.ks * d.ks, d.co, d.ci_total
+        nw = co * ci * taps
+        assert taps <= WRED_TILE and nw < 2 ** 31
+        pw = d.partial_w or 0
+        vec = 1 if nw % 4 == 0 and pw % 16 == 0 else 0
+        tile = WRED_TILE_DEEP if vec and d.nsplit > 4 else WRED_TILE  # (a deep site keeps four chain sums per element in LDS)
+        if d.layout == 1:  # rows a = ci, columns b = co; the gradient's runs are na * taps long
+            rows, inner = ci, co
+            na = min(rows, max(1, -(-64 // taps)))
+            nb = _even_cut(inner, max(1, tile // (na * taps)))
+            na = min(rows, max(1, tile // (taps * nb)))
+        else:  # rows a = co, columns b = ci; the runs are nb * taps long
+            rows, inner = co, ci
+            nb = _even_cut(inner, max(1, tile // taps))
+            na = min(rows, max(1, tile // (taps * nb)))
+        for a0 in range(0, rows, na):
+            for b0 in range(0, inner, nb):
+                it = _lib.WredItem()
+                it.partial, it.grad, it.kind, it.nsplit, it.split_stride = d.partial_w, d.grad_w, 0, d.nsplit, nw
+                it.vec, it.accumulate, it.unscale = vec, d.accumulate, d.unscale
+                it.taps, it.inner, it.ci_total, it.layout = taps, inner, ci, d.layout
+                it.a0, it.na, it.b0, it.nb = a0, min(na, rows - a0), b0, min(nb, inner - b0)
+                it.v4 = 1 if vec and inner % 4 == 0 and it.b0 % 4 == 0 and it.nb % 4 == 0 else 0
+                assert 0 < it.na * taps * it.nb <= tile
+                items.append(it)
+        if d.grad_b:
+            for b0 in range(0, co, 1024):
+                it = _lib.WredItem()
+                it.partial, it.grad, it.kind, it.nsplit, it.split_stride = d.partial_b, d.grad_b, 1, d.nsplit, co
+                it.accumulate, it.unscale, it.b0, it.nb = d.accumulate, d.unscale, b0, min(1024, co - b0)
+                items.append(it)
+    items.sort(key=lambda it: -(it.nsplit if it.kind == 1 or not it.vec else (it.nsplit + 3) // 4))
+    return (_lib.WredItem * len(items))(*items)
+
+
 class WgradMixin:
     @staticmethod
     def _needs_wgrad(site):
@@ -276,11 +331,16 @@ class WgradMixin:
                 csite += [i] * nch
                 cidx += list(range(nch))
             arr = (_lib.WredDesc * len(descs))(*descs)
+            items = plan_wred_items(descs)
             tab = (self._to_dev(bytes(arr)), torch.tensor(csite, dtype=torch.int32, device=self.device),
-                   torch.tensor(cidx, dtype=torch.int32, device=self.device), len(csite))
+                   torch.tensor(cidx, dtype=torch.int32, device=self.device), len(csite),
+                   self._to_dev(bytes(items)), len(items))
             self._red_tabs[sig] = tab
-        d, cs, ci, n = tab
-        self.lib.wgrad_reduce(d.data_ptr(), cs.data_ptr(), ci.data_ptr(), n, stream)
+        d, cs, ci, n, items, nitems = tab
+        if _WRED_REF:
+            self.lib.wgrad_reduce_ref(d.data_ptr(), cs.data_ptr(), ci.data_ptr(), n, stream)
+        else:
+            self.lib.wgrad_reduce_tiles(items.data_ptr(), nitems, stream)
         self.launches += 1
         for site, _, _ in events:
             if site.conv.weight.requires_grad:

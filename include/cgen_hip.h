@@ -251,6 +251,32 @@ typedef struct cgen_wred_desc { /* split-K partials -> OIHW f32 gradient (+bias 
 int cgen_wgrad_reduce(const cgen_wred_desc* descs_dev, const int32_t* chunk_site_dev, const int32_t* chunk_index_dev,
                       int32_t nchunks, cgen_stream_t stream);
 
+/* The per-element kernels of the two launches above under names of their own (same tables): they define the image layouts and the
+ * order of the sums, and what replaces them is tested against them byte for byte (additive in ABI 411: new symbols only). */
+int cgen_weight_prep_ref(const cgen_wprep_desc* descs_dev, const int32_t* chunk_site_dev, const int32_t* chunk_index_dev,
+                         int32_t nchunks, cgen_stream_t stream);
+
+/* cgen_wgrad_reduce, tiled (csrc/multitensor.hip; additive in ABI 411: one new struct, new symbols).  One workgroup: a TILE of a
+ * site's partials, rows [a0, a0 + na) x every tap, columns [b0, b0 + nb) of the partial layout (layout 0: a = Co, b = Ci, inner = Ci_total; layout 1: a = Ci, b = Co, inner = Co), at most 2048 elements (1024 for a site with more than four splits on the 16-byte path), or
+ * (kind 1) the bias gradient of channels [b0, b0 + nb).  The four split chains of cgen_wgrad_reduce go to different lanes and are
+ * combined in its order; the sums leave LDS as contiguous runs of the OIHW gradient (nb * taps floats in layout 0, na * taps in layout 1). */
+typedef struct cgen_wred_item {
+  const float* partial; /* the site's partial_w (kind 0) or partial_b (kind 1) */
+  float* grad;          /* the site's grad_w or grad_b */
+  int32_t kind, nsplit;
+  int32_t split_stride; /* elements between two splits: Co * Ci_total * KS * KS, or Co for the bias */
+  int32_t vec;          /* 1: the site takes cgen_wgrad_reduce's 16-byte path (four chains); 0: plain split order */
+  int32_t v4;           /* 1: 16-byte loads are possible (inner, b0, nb, split_stride multiples of 4, partial 16-byte aligned) */
+  int32_t accumulate;
+  float unscale;
+  int32_t taps, inner, ci_total, layout;
+  int32_t a0, na, b0, nb;
+  int32_t reserved;
+} cgen_wred_item;
+int cgen_wgrad_reduce_tiles(const cgen_wred_item* items_dev, int32_t nitems, cgen_stream_t stream);
+int cgen_wgrad_reduce_ref(const cgen_wred_desc* descs_dev, const int32_t* chunk_site_dev, const int32_t* chunk_index_dev,
+                          int32_t nchunks, cgen_stream_t stream);
+
 /* ------------------------------------------------------------------ element-wise / data movement
  * aten::avg_pool2d fwd/bwd (vae.py:79-83), upsample_nearest2d (+ learned per-res bias, vae.py:251-262),
  * F.pad / slicing / clone (vae.py:131-133, 241), repeat of bias[1] (vae.py:233), pa_sto scaling (vae.py:244-247),

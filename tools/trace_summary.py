@@ -13,7 +13,7 @@ for r in rows:
     n = re.sub(r"\(.*", "", r["Kernel_Name"]).replace("void cgen::", "").replace("cgen::", "")
     agg[n][0] += 1
     agg[n][1] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-steps = agg.get("wred_kernel", [1])[0] or 1
+steps = sum(v[0] for k, v in agg.items() if k.startswith("wred_kernel")) or 1  # (wred_kernel_tiled by default, wred_kernel with CGEN_WRED_REF=1)
 tot = sum(v[1] for v in agg.values())
 print("steps %d, sum of kernel durations %.2f ms/step" % (steps, tot / 1e3 / steps))
 for k, v in sorted(agg.items(), key=lambda kv: -kv[1][1])[:top]:
