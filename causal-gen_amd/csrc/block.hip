@@ -44,18 +44,6 @@ constexpr int b3_ndi(int th) { return ((th + 4) * B3_HW + 47) / 48; }           
 constexpr int b3_xbytes(int th) { return 4 * b3_ndi(th) * 12 * B3_XS + 64; }     // one ring slot (whole instructions + the overhang of the last one): 19 264 / 26 944
 constexpr int b3_nmp(int th) { return (th + 2) * B3_MW; }                         // bottleneck pixels: 180 / 252
 
-struct B3Div { uint32_t mul, shift; };
-static inline B3Div b3_mkdiv(uint32_t d) {
-  B3Div f;
-  if (d == 1) { f.mul = 0; f.shift = 0; return f; }
-  uint32_t sh = 0;
-  while ((1u << sh) < d) ++sh;
-  f.shift = sh;
-  f.mul = (uint32_t)((((uint64_t)1 << (32 + sh)) + d - 1) / d - ((uint64_t)1 << 32));
-  return f;
-}
-__device__ __forceinline__ int b3_div(int n, const B3Div& f) { return (int)(((uint64_t)__umulhi((uint32_t)n, f.mul) + (uint32_t)n) >> f.shift); }
-
 struct BV3 { const char* p; int sn, sh, sw; };  // 32-bit BYTE strides (the host checks every view spans < 2^31 bytes)
 struct B3Out {
   const char* w;      // phase-B fragment image [pair][K16-step][lane][8]
@@ -69,14 +57,14 @@ struct B3P {
   int tiles_x, tiles_y, ntiles, ctot8;
   int ns, wb_persist, scratch_off, bias_off;
   int tm_off, tm_bytes, pad1, pad2;  // ring slots; phase-B weights persistent in registers; LDS offset of the second reduction scratch half (0: none)
-  B3Div d_tx, d_ty;
+  Div32 d_tx, d_ty;
   BV3 seg[3];
   int seg_koff[4];  // first CHUNK of segment s (segments are padded to whole 32-channel chunks); [nseg] = nch
   int seg_c8[3];
   // small-image instance (blk3s, images up to 14 pixels wide): a workgroup owns `s_rows` output rows of one image
   int small, s_rows, s_strips, s_nmb;  // s_nmb: 32-row blocks of the bottleneck (1 or 2)
   int s_mid_off, s_kt_off, s_red_off, s_dbg, s_segk0[3], s_segg[3];  // LDS offsets; first chunk / 16-byte groups per pixel of segment s
-  B3Div s_dg1, s_dxw, s_dw, s_dstrips, s_dnb;
+  Div32 s_dg1, s_dxw, s_dw, s_dstrips, s_dnb;
   // row-streaming instance (blk3r): strips of 32 columns x r_rs rows
   int rows, r_rs, r_sx, r_sy, r_res_tile, r_pad;
   const char* wA16;  // 16-row image of conv1 ([tap][chunk][lane][8]; cgen_weight_prep modes 6 / 7)
@@ -260,8 +248,8 @@ __device__ __forceinline__ void blk3_body(const B3P& p, const int bid, const int
   const int pg0 = NPG == 4 ? 0 : (NPG == 2 ? PGW * (wave >> 1) : PGW * wave);
 
   auto tile_of = [&](const int tile, int& n, int& y0, int& x0) {
-    const int b1 = b3_div(tile, p.d_tx), tx = tile - b1 * p.tiles_x;
-    n = b3_div(b1, p.d_ty);
+    const int b1 = div32(tile, p.d_tx), tx = tile - b1 * p.tiles_x;
+    n = div32(b1, p.d_ty);
     y0 = (b1 - n * p.tiles_y) * TH; x0 = tx * B3_TW;
   };
   // which of this lane's five halo pixels of tile (y0, x0) lie inside the image (once per tile, not per chunk)
@@ -897,7 +885,7 @@ __device__ __forceinline__ void blk3s_body(const B3P& p, const int bid, const in
     const int item = bid;
     B3sK<4> KA;
     B3sK<8> KB;
-    const int n = b3_div(item, p.s_dstrips), y0 = (item - n * p.s_strips) * R;
+    const int n = div32(item, p.s_dstrips), y0 = (item - n * p.s_strips) * R;
     const int Rr = min(R, H - y0), NOP = Rr * W;
     // ---- input rows y0 - 2 .. y0 + R + 1, columns -1 .. W, every segment (virtual cat), -> LDS by DMA: one 16-byte slot per lane,
     // zeros outside the image / past a segment's channels / in the pad slot.  The first thing a workgroup does: everything below
@@ -911,8 +899,8 @@ __device__ __forceinline__ void blk3s_body(const B3P& p, const int bid, const in
       for (int ii = wave; ii < ((p.s_dbg & 1) ? 0 : ninst); ii += B3S_NW) {
         const int iu = __builtin_amdgcn_readfirstlane(ii);
         const int sl = min(iu * 64 + lane, nslots - 1);
-        const int pxl = b3_div(sl, p.s_dg1), g = sl - pxl * G1;
-        const int ry = b3_div(pxl, p.s_dxw), cx = pxl - ry * XW;
+        const int pxl = div32(sl, p.s_dg1), g = sl - pxl * G1;
+        const int ry = div32(pxl, p.s_dxw), cx = pxl - ry * XW;
         const int iy = y0 - 2 + ry, ix = cx - 1;
         const bool s1 = g >= g1, s2 = g >= g2;
         const char* sp = s2 ? p2 : (s1 ? p1 : p0);
@@ -932,7 +920,7 @@ __device__ __forceinline__ void blk3s_body(const B3P& p, const int bid, const in
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       const int mc = min(32 * g + px, NMP - 1);
-      mr[g] = b3_div(mc, p.s_dw); mx[g] = mc - mr[g] * W;
+      mr[g] = div32(mc, p.s_dw); mx[g] = mc - mr[g] * W;
     }
     const bool fjob = wave < 4 * nmb && (fng == 0 || NMP > 32);
     const int fiy = y0 - 1 + mr[fng];
@@ -949,7 +937,7 @@ __device__ __forceinline__ void blk3s_body(const B3P& p, const int bid, const in
     // ---- tables, zeros of the bottleneck tile (the border columns and the rows outside the image stay zero: conv2's padding)
     {
       for (int u = tid; u < 128; u += 64 * B3S_NW) {
-        const int uu = min(u, 2 * nks - 1), tq = b3_div(uu, p.s_dnb), tp = min(tq, 8), gq = uu - tq * NB;
+        const int uu = min(u, 2 * nks - 1), tq = div32(uu, p.s_dnb), tp = min(tq, 8), gq = uu - tq * NB;
         KT[u] = ((tp / 3) * B3S_MW + tp % 3) * MS + gq * 16;
       }
       for (int sidx = tid; sidx < nst + 16; sidx += 64 * B3S_NW) {
@@ -1116,7 +1104,7 @@ __device__ __forceinline__ void blk3s_body(const B3P& p, const int bid, const in
         const int pair = npg == 2 ? blk >> 1 : blk, pg = npg == 2 ? blk & 1 : 0;
         const int SK = (nks + KP - 1) / KP, k0 = min(kp * SK, nks - 1);
         const int o = 32 * pg + px, oc = min(o, NOP - 1);
-        const int oy = b3_div(oc, p.s_dw), ox = oc - oy * W;
+        const int oy = div32(oc, p.s_dw), ox = oc - oy * W;
         const bool ev = work && o < NOP;
         const int ch0 = pair * 32 + 16 * kg, gy = y0 + oy;
         Epi E[2];
@@ -1469,7 +1457,7 @@ static bool b3_view(const cgen_view& v, int n, int h, int w, BV3& o) {
 static void b3_tiles(B3P& p, int th) {
   p.tiles_x = ceil_div(p.W, B3_TW); p.tiles_y = ceil_div(p.H, th);
   p.ntiles = p.N * p.tiles_x * p.tiles_y;
-  p.d_tx = b3_mkdiv(p.tiles_x); p.d_ty = b3_mkdiv(p.tiles_y);
+  p.d_tx = mk_div32(p.tiles_x); p.d_ty = mk_div32(p.tiles_y);
 }
 
 static size_t b3s_lds(const B3P& p) { return (size_t)p.s_kt_off + (128 + 18 * p.nch + 16) * 4; }  // the two K-axis tables end the image
@@ -1547,12 +1535,12 @@ static int b3_fill(const cgen_block3_args* a, B3P& p) {
     if (R > p.H) R = p.H;
     p.s_rows = R; p.s_strips = ceil_div(p.H, R); p.s_nmb = (p.b + 31) / 32;
     p.ntiles = p.N * p.s_strips;
-    p.s_dxw = b3_mkdiv(p.W + 2); p.s_dw = b3_mkdiv(p.W); p.s_dstrips = b3_mkdiv(p.s_strips);
+    p.s_dxw = mk_div32(p.W + 2); p.s_dw = mk_div32(p.W); p.s_dstrips = mk_div32(p.s_strips);
     for (int s = 0; s < a->nseg; ++s) {
       p.s_segk0[s] = p.seg_koff[s];
       p.s_segg[s] = 4 * ((a->seg[s].c + 31) / 32);
     }
-    p.s_dg1 = b3_mkdiv(p.nch * 4 + 1); p.s_dnb = b3_mkdiv(p.b / 8);
+    p.s_dg1 = mk_div32(p.nch * 4 + 1); p.s_dnb = mk_div32(p.b / 8);
     const int nb8 = p.b / 8, nbs = (nb8 & 1) ? nb8 : nb8 + 1;
     const int xbytes = (((R + 4) * (p.W + 2) * (p.nch * 4 + 1) + 63) / 64) * 1024;  // whole DMA instructions
     p.s_red_off = 0;  // the exchange buffer [wave][pixel group][16 floats][64 lanes] (64 KiB) shares the input tile's memory: the tile is dead after phase A

@@ -41,18 +41,6 @@ __device__ uint4 g_b4zero[2];  // 32 bytes of zeros: source of out-of-image / pa
 #define B4_N2 128
 #define B4_BIAS_BYTES (3 * 64 * 4 + 256 * 4)
 
-struct B4Div { uint32_t mul, shift; };
-static inline B4Div b4_mkdiv(uint32_t d) {
-  B4Div f;
-  if (d == 1) { f.mul = 0; f.shift = 0; return f; }
-  uint32_t sh = 0;
-  while ((1u << sh) < d) ++sh;
-  f.shift = sh;
-  f.mul = (uint32_t)((((uint64_t)1 << (32 + sh)) + d - 1) / d - ((uint64_t)1 << 32));
-  return f;
-}
-__device__ __forceinline__ int b4_div(int n, const B4Div& f) { return (int)(((uint64_t)__umulhi((uint32_t)n, f.mul) + (uint32_t)n) >> f.shift); }
-
 struct B4V { const char* p; int sn, sh, sw; };  // 32-bit BYTE strides (the host checks every view spans < 2^31 bytes)
 struct B4Out {
   const char* w;      // phase-3 fragment image [32-row block][16-channel group of the bottleneck][lane][8]
@@ -66,7 +54,7 @@ struct B4P {
   int nch0, bc8, nout, xcd_order;  // phase-0 chunks of 32 input channels; bottleneck width rounded up to 8 (stored channel groups)
   int tiles_x, tiles_y, ntiles, pad1;
   int inv[3][2];  // ceil(65536 / columns) of phases 0, 1, 2 (tile width + 4, + 2, + 0) for a full-width tile [0] and the last tile of a row [1]
-  B4Div d_tx, d_ty;
+  Div32 d_tx, d_ty;
   B4V seg[3];
   int seg_nch[3], seg_c8[3];
   const char* w[3];       // fragment images of phases 0, 1, 2
@@ -281,8 +269,8 @@ __device__ __forceinline__ void blk4_body(const B4P& p, const int tile) {
   const float4* const lut0 = lut + 192;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int px = lane & 31, kg = lane >> 5;
-  const int b1 = b4_div(tile, p.d_tx), tx = tile - b1 * p.tiles_x;
-  const int n = b4_div(b1, p.d_ty);
+  const int b1 = div32(tile, p.d_tx), tx = tile - b1 * p.tiles_x;
+  const int n = div32(b1, p.d_ty);
   const int y0 = (b1 - n * p.tiles_y) * B4_TH, x0 = tx * B4_TW;
   const int th = min(B4_TH, p.H - y0), tw = min(B4_TW, p.W - x0);  // the tile's actual extent
   const int lastx = tx == p.tiles_x - 1 ? 1 : 0;
@@ -544,7 +532,7 @@ static int b4_fill(const cgen_block4_args* a, B4P& p, int& nb8) {
   p.ntiles = (int)nt;
   static const int xcd_env = [] { const char* e = getenv("CGEN_BLK4_XCD"); return e ? atoi(e) : 1; }();
   p.xcd_order = xcd_env && nt >= 512;  // (launches of at least two tiles per CU: below that placement decides nothing)
-  p.d_tx = b4_mkdiv(p.tiles_x); p.d_ty = b4_mkdiv(p.tiles_y);
+  p.d_tx = mk_div32(p.tiles_x); p.d_ty = mk_div32(p.tiles_y);
   {
     const int twl = p.W - B4_TW * (p.tiles_x - 1);  // width of a row's last tile
     for (int k = 0; k < 3; ++k) {

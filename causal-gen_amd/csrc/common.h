@@ -3,9 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/cgen_hip.h"
+#include "fastdiv.h"
 
 namespace cgen {
 
@@ -267,5 +269,11 @@ struct Philox {
 };
 
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// integer tuning / ablation knob from the environment (`static const int x = env_int(...)` reads it once)
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 }  // namespace cgen

@@ -1,11 +1,9 @@
 // Streaming weight-gradient kernel, round 5 (csrc/wgrad3.hip): host-side plan + launch interface used by the C-ABI entry points
-// in conv.hip (cgen_conv2d_wgrad, cgen_conv2d_wgrad_plan, cgen_conv2d_wgrad_batch_plan / _run).
+// in wgrad.hip (cgen_conv2d_wgrad, cgen_conv2d_wgrad_plan, cgen_conv2d_wgrad_batch_plan / _run).
 #pragma once
 #include "common.h"
 
 namespace cgen {
-
-struct W3Div { uint32_t mul, shift; };
 
 // One operand tile in LDS (P: unshifted, wide; S: shifted by the taps, narrow).  Pixels are laid out linearly (row-major over
 // rows x rowpx) at `sp` bytes per pixel; a DMA instruction fills `ppi` whole pixels (gpp 16-byte groups each).
@@ -20,8 +18,8 @@ struct W3Op {
   int ninstr;  // DMA instructions per tile
   int halo;    // 0 / 1
   int bytes;   // LDS bytes reserved for the tile (ninstr * ppi * sp)
-  W3Div d_row; // division by rowpx
-  W3Div d_gpp; // division by gpp
+  Div32 d_row; // division by rowpx
+  Div32 d_gpp; // division by gpp
 };
 
 struct Wg3P {
@@ -29,7 +27,7 @@ struct Wg3P {
   int x_is_s;   // 1: S = act(X) (n = tap * cs8 + ci), P = grad_out (rows = co); 0: S = grad_out (n = flipped tap * cs8 + co), P = act(X) (rows = ci)
   int th, tw, tiles_x, tiles_y, ntiles, tps, nsplit;
   int ksteps, kst_rows;  // K16-steps per tile; tile rows per K-step (1: tw = 16, 2: tw = 8)
-  W3Div d_tx, d_ty;
+  Div32 d_tx, d_ty;
   W3Op P, S;
   int pwin_c, n_pwin, MP, NS;  // channels per P window (multiple of 32), windows, P fragments per window, S fragments
   int WM, WN, WK;              // wave grid: P-fragment blocks x S-fragment blocks x K split (WM * WN * WK = 4)

@@ -1,4 +1,4 @@
-// Streaming weight gradient for gfx950 (MI355X), round 5.  Replaces wgrad_tile_mega_kernel (conv.hip) for every shape it serves.
+// Streaming weight gradient for gfx950 (MI355X), round 5.  Replaces wgrad_tile_mega_kernel (wgrad.hip) for every shape it serves.
 //   dW[co][dy][dx][ci] = sum_px G[px][co] * act(X)[px + (dy-1, dx-1)][ci]        (aten::convolution_backward, weight part;
 //                                                                                  reference: src/vae.py:53-55, 63-65 through autograd)
 //
@@ -41,19 +41,6 @@ __device__ uint4 g_w3zero[4];  // DMA source of out-of-image pixels
 #endif
 #define W3_PN 6  // DMA instructions per wave and tile whose lane offsets live in registers: P tile, S tile
 #define W3_SN 3
-
-static inline W3Div mk_w3div(uint32_t d) {  // round-up method, exact for 0 <= n < 2^31 (as FastDiv in conv.hip)
-  W3Div f;
-  if (d <= 1) { f.mul = 0; f.shift = 0; return f; }
-  uint32_t sh = 0;
-  while ((1u << sh) < d) ++sh;
-  f.shift = sh;
-  f.mul = (uint32_t)((((uint64_t)1 << (32 + sh)) + d - 1) / d - ((uint64_t)1 << 32));
-  return f;
-}
-__device__ __forceinline__ int w3div(int n, const W3Div f) {
-  return (int)(((uint64_t)__umulhi((uint32_t)n, f.mul) + (uint32_t)n) >> f.shift);
-}
 
 // one LDS-DMA instruction (16 B per lane -> LDS at `lds` + 16 * lane) the compiler's wait-count pass does not see (block.hip)
 __device__ __forceinline__ void w3_dma16(const char* src, const uint32_t lds) {
@@ -367,7 +354,7 @@ struct W3Lane {
 // (concatenated) conv input, else the output gradient; channels [c0, c0 + width) of the operand are staged
 __device__ __forceinline__ W3Lane w3_lane(const Wg3P* __restrict__ gp, const W3Op& o, const bool is_x, const int c0, const int width, const int lane) {
   W3Lane L;
-  L.pl = w3div(lane, o.d_gpp);
+  L.pl = div32(lane, o.d_gpp);
   const int grp = lane - L.pl * o.gpp;
   L.active = L.pl < o.ppi;
   const int c = c0 + grp * 8;
@@ -392,7 +379,7 @@ __device__ __forceinline__ void w3_issue_op(const W3Op& o, const W3Lane& L, cons
   const int step = o.ppi * o.sp;
   for (int i = first; i < o.ninstr; i += 4) {
     const int lin = i * o.ppi + L.pl;
-    const int ry = w3div(lin, o.d_row), rx = lin - ry * o.rowpx;
+    const int ry = div32(lin, o.d_row), rx = lin - ry * o.rowpx;
     const int gy = y0 + ry, gx = x0 + rx;
     const bool ok = L.data && lin < o.npx && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
     const char* src = ok ? L.base + (noff + gy * L.sh + gx * L.sw) : zero;
@@ -437,14 +424,14 @@ __device__ __forceinline__ void wg3_body(const Wg3P* __restrict__ gp, const int 
 #pragma unroll
     for (int k = 0; k < W3_PN; ++k) {
       const int lin = (wave + 4 * k) * P.ppi + LP.pl;
-      const int ry = w3div(lin, P.d_row), rx = lin - ry * P.rowpx;
+      const int ry = div32(lin, P.d_row), rx = lin - ry * P.rowpx;
       poff[k] = ry * LP.sh + rx * LP.sw;
       if (LP.data && lin < P.npx && wave + 4 * k < P.ninstr) vmask |= 1u << k;
     }
 #pragma unroll
     for (int k = 0; k < W3_SN; ++k) {
       const int lin = (wave + 4 * k) * S.ppi + LS.pl;
-      const int ry = w3div(lin, S.d_row), rx = lin - ry * S.rowpx;
+      const int ry = div32(lin, S.d_row), rx = lin - ry * S.rowpx;
       soff[k] = ry * LS.sh + rx * LS.sw;
       syx[k >> 1] |= (uint32_t)((ry & 63) << 6 | (rx & 63)) << (12 * (k & 1));
       if (LS.data && lin < S.npx && wave + 4 * k < S.ninstr) vmask |= 1u << (8 + k);
@@ -456,9 +443,9 @@ __device__ __forceinline__ void wg3_body(const Wg3P* __restrict__ gp, const int 
   const int t_begin = sp_i * gp->tps, t_end = min(gp->ntiles, t_begin + gp->tps);
   int q_n, q_ty, q_tx;
   {
-    const int b1 = w3div(t_begin, gp->d_tx);
+    const int b1 = div32(t_begin, gp->d_tx);
     q_tx = t_begin - b1 * tiles_x;
-    q_n = w3div(b1, gp->d_ty);
+    q_n = div32(b1, gp->d_ty);
     q_ty = b1 - q_n * tiles_y;
   }
   // The requests of a tile are SPREAD over the first K16-steps of the tile being consumed (positions 0..3): a burst of ~19 KiB right
@@ -938,7 +925,7 @@ static void w3_mk_op(W3Op& o, int c8_staged, int sp, int rows, int rowpx, int ha
   o.rows = rows; o.rowpx = rowpx; o.npx = rows * rowpx; o.halo = halo;
   o.ninstr = (o.npx + o.ppi - 1) / o.ppi;
   o.bytes = o.ninstr * o.ppi * sp;
-  o.d_row = mk_w3div(rowpx); o.d_gpp = mk_w3div(o.gpp);
+  o.d_row = mk_div32(rowpx); o.d_gpp = mk_div32(o.gpp);
   (void)c8_staged;
 }
 
@@ -1084,7 +1071,7 @@ bool wg3_plan(const cgen_wgrad_args* a, Wg3Plan& g) {
   q.ksteps = q.th * q.tw / 16;
   q.tiles_x = (a->w + q.tw - 1) / q.tw; q.tiles_y = (a->h + q.th - 1) / q.th;
   q.ntiles = a->n * q.tiles_x * q.tiles_y;
-  q.d_tx = mk_w3div(q.tiles_x); q.d_ty = mk_w3div(q.tiles_y);
+  q.d_tx = mk_div32(q.tiles_x); q.d_ty = mk_div32(q.tiles_y);
   if (ceil_div(q.P.ninstr, 4) + ceil_div(q.S.ninstr, 4) > 48 / std::max(1, q.nslot - 2)) {
     // (more requests per wave in flight than the counted-wait table holds: w3_vmwait would fall back to vmcnt(0) -- correct, slower)
   }

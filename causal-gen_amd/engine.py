@@ -236,7 +236,7 @@ class ConvSite:
 
 
 class Engine(WgradMixin):
-    CHUNK = 1024  # elements per block of the multi-tensor kernels (MT_CHUNK in conv.hip)
+    CHUNK = 1024  # elements per block of the multi-tensor kernels (MT_CHUNK in multitensor.hip)
 
     def __init__(self, device, dtype="f32"):
         rawlib = _lib.require_gpu()

@@ -1,5 +1,5 @@
 """Register / scratch / occupancy table of the kernels in one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/kernel_regs.py causal-gen_amd/csrc/conv.hip [name-substring]"""
+usage: python tools/kernel_regs.py causal-gen_amd/csrc/UNIT.hip [name-substring]   (conv.hip, wgrad.hip, wgrad3.hip, block.hip, ...)"""
 import re, subprocess, sys, os
 src = sys.argv[1]
 pat = sys.argv[2] if len(sys.argv) > 2 else ""
