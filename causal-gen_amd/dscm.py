@@ -16,6 +16,7 @@ from torch import Tensor, nn
 
 from . import _lib
 from .engine import StaticParents, compact_parents
+from .step_tail import capture
 
 _UKBB_MIN_MAX = {"age": (73.0, 44.0), "brain_volume": (1629520.0, 841919.0), "ventricle_volume": (157075.0, 7613.27001953125)}
 _UKBB_LOG_STATS = {"age": (4.112339973449707, 0.11769197136163712), "brain_volume": (13.965583801269531, 0.09537758678197861),
@@ -108,10 +109,7 @@ class GraphedCounterfactual:
         if ent is None:
             out = counterfactual(vae, x, parents, cf_parents, **self.kw)  # eager warm-up: sizes the arena, builds tables
             sx, sp, sc = x.clone(), StaticParents(parents), StaticParents(cf_parents)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):  # (a live NCCL watchdog thread must not invalidate the capture: train.CAPTURE_MODE)
-                so = counterfactual(vae, sx, sp.t, sc.t, **self.kw)
+            g, so = capture(lambda: counterfactual(vae, sx, sp.t, sc.t, **self.kw))
             self.graphs[key] = (g, sx, sp, sc, so)
             return out
         g, sx, sp, sc, so = ent

@@ -22,7 +22,7 @@ from torch import nn
 
 from . import _lib
 from .pgm import ConditionalAffine, DenseNN, LinearSpline
-from .predictor_train import _flatten
+from .step_tail import NORM, Flat, HyperParams, StepTail, capture, check_warmup
 
 _KINDS = {"bernoulli": _lib.PGM_BERNOULLI, "categorical": _lib.PGM_CATEGORICAL, "spline": _lib.PGM_SPLINE, "affine": _lib.PGM_AFFINE,
           "gumbel_max": _lib.PGM_GUMBEL_MAX}
@@ -47,17 +47,6 @@ def default_columns(pgm):
         cols[var] = o
         o += width[var]
     return cols, o
-
-
-class _Flat:
-    """A PGM with its parameters flattened into one f32 buffer (online model or EMA copy)."""
-
-    def __init__(self, pgm, dev):
-        pgm.to(dev)
-        self.pgm = pgm
-        named = list(pgm.named_parameters())
-        self.names, self.params = [n for n, _ in named], [p for _, p in named]
-        self.flat_p, self.p_off = _flatten(self.params, dev)
 
 
 def _mlp_of(m):
@@ -132,12 +121,12 @@ class PgmTrainStep:
 
     def __init__(self, pgm, lr=1e-4, wd=0.1, betas=(0.9, 0.999), eps=1e-8, grad_clip=200.0, lr_warmup_steps=1, ema_rate=0.999, ema=True,
                  use_graph=True, ema_update_after=100, columns=None, ncol=None, device="cuda"):
-        if int(lr_warmup_steps) <= 0:
-            raise ValueError(f"lr_warmup_steps must be > 0 (got {lr_warmup_steps}): the linear warm-up divides by it")
+        check_warmup(lr_warmup_steps)
         self.lib = _lib.require_gpu()
         dev = self.device = torch.device(device)
-        self.lr, self.wd, self.betas, self.eps, self.grad_clip = float(lr), float(wd), (float(betas[0]), float(betas[1])), float(eps), float(grad_clip)
-        self.lr_warmup_steps, self.ema_rate, self.ema_update_after = int(lr_warmup_steps), float(ema_rate), int(ema_update_after)
+        # (no norm threshold in sup_epoch: only a non-finite norm or a NaN loss drops the step)
+        self.hp = HyperParams(float(lr), (float(betas[0]), float(betas[1])), float(eps), float(wd), float(grad_clip), float("inf"),
+                              int(lr_warmup_steps), float(ema_rate), int(ema_update_after))
         self.use_graph = use_graph
         if columns is None:
             columns, width = default_columns(pgm)
@@ -150,18 +139,17 @@ class PgmTrainStep:
         if ema:
             self.ema_model = copy.deepcopy(pgm)
             self.ema_model.requires_grad_(False)
-            self._ema = _Flat(self.ema_model, dev)
+            self._ema = Flat(self.ema_model.to(dev).named_parameters(), dev)
         self.model = pgm
-        self._on = _Flat(pgm, dev)
+        self._on = Flat(pgm.to(dev).named_parameters(), dev)
         n = self._on.flat_p.numel()
         self.flat_g = torch.zeros(n, device=dev)
-        self.m = torch.zeros(n, device=dev)
-        self.v = torch.zeros(n, device=dev)
+        self.tail = StepTail(self.lib, n, dev, self.NORM_BLOCKS)
+        self.stats = self.tail.stats  # host read of the device-side step state (one sync)
+        self.m, self.v, self.state, self.partial = self.tail.m, self.tail.v, self.tail.state, self.tail.partial
         on = self._on
         self.recs = build_records(pgm, self.columns, self.ncol, {id(p): self.flat_g.data_ptr() + 4 * o for p, o in zip(on.params, on.p_off)})
         self.nmech = len(self.recs)
-        self.state = torch.zeros(8, device=dev)
-        self.partial = torch.zeros(self.NORM_BLOCKS, device=dev)
         self.out3 = torch.zeros(3, device=dev)  # [-, summed log-probability, 0]: what cgen_clip_decide tests for NaN
         self.res = torch.zeros(2, device=dev)   # [mean loss, gradient norm] of the last step
         self._statics, self._graphs = {}, {}
@@ -228,21 +216,13 @@ class PgmTrainStep:
         torch.div(self.out3[1:2], -float(ent["B"]), out=self.res[0:1])
 
     def _optim(self):
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        g = self.flat_g
-        self.lib.sumsq_partial(g.data_ptr(), g.numel(), self.partial.data_ptr(), self.NORM_BLOCKS, st)
-        # (no norm threshold in sup_epoch: only a non-finite norm or a NaN loss drops the step)
-        self.lib.clip_decide(self.partial.data_ptr(), self.NORM_BLOCKS, self.out3.data_ptr(), self.grad_clip, float("inf"),
-                             self.state.data_ptr(), st)
-        q = _lib.AdamwArgs()
-        q.p, q.g, q.m, q.v = self._on.flat_p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
-        q.ema, q.count = (self._ema.flat_p.data_ptr() if self.ema_model is not None else None), g.numel()
-        q.lr, q.beta1, q.beta2, q.eps, q.wd = self.lr, self.betas[0], self.betas[1], self.eps, self.wd
-        q.ema_beta, q.warmup_steps, q.ema_update_after = self.ema_rate, self.lr_warmup_steps, self.ema_update_after
-        q.state_dev = self.state.data_ptr()
-        self.lib.adamw_ema(C.byref(q), st)
-        self.lib.step_commit(self.state.data_ptr(), st)
-        self.res[1:2].copy_(self.state[1:2])
+        self.tail.run(self.hp, self._on.flat_p, self.flat_g, self._ema.flat_p if self.ema_model is not None else None, self.out3,
+                      torch.cuda.current_stream(self.device).cuda_stream)
+        self.res[1:2].copy_(self.state[NORM:NORM + 1])
+
+    def _fwd_bwd_optim(self, ent):
+        self._fwd_bwd(ent)
+        self._optim()
 
     def _run(self, key, ent):
         self.it += 1
@@ -250,17 +230,9 @@ class PgmTrainStep:
         if graph is not None:
             graph.replay()
         else:
-            self._fwd_bwd(ent)
-            self._optim()
+            self._fwd_bwd_optim(ent)
             if self.use_graph:
-                from .train import CAPTURE_MODE
-
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode=CAPTURE_MODE):
-                    self._fwd_bwd(ent)
-                    self._optim()
-                self._graphs[key] = graph
+                self._graphs[key], _ = capture(lambda: self._fwd_bwd_optim(ent))
         out = self.res.clone()
         return {"loss": out[0], "grad_norm": out[1]}
 
@@ -294,18 +266,12 @@ class PgmTrainStep:
         on = self._on
         return self.res[0].clone(), {n: self.flat_g[o:o + p.numel()].view(p.shape).clone() for n, p, o in zip(on.names, on.params, on.p_off)}
 
-    def stats(self):
-        """Host read of the device-side step state (one sync)."""
-        s = self.state.cpu().tolist()
-        return dict(grad_norm=s[1], clip_coef=s[2], skipped_last=bool(s[3]), n_skipped=int(s[4]), opt_steps=int(s[5]))
-
     def state_dict(self):
         """The reference checkpoint's keys (train_pgm.py:536-545): ``model_state_dict`` / ``ema_model_state_dict`` with the
         reference's parameter names (``load_reference_state_dict`` takes either), ``optimizer_state_dict`` (flat AdamW moments in
         ``named_parameters`` order, and the device step state)."""
         sd = {"step": self.it, "model_state_dict": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-              "optimizer_state_dict": {"exp_avg": self.m.clone(), "exp_avg_sq": self.v.clone(), "state": self.state.clone(),
-                                       "names": list(self._on.names)}}
+              "optimizer_state_dict": self.tail.flat_optimizer_state(self._on.names)}
         if self.ema_model is not None:
             sd["ema_model_state_dict"] = {k: v.detach().clone() for k, v in self.ema_model.state_dict().items()}
         return sd
@@ -317,9 +283,5 @@ class PgmTrainStep:
             self.ema_model.load_reference_state_dict(sd["ema_model_state_dict"])
         opt = sd.get("optimizer_state_dict")
         if opt is not None and "exp_avg" in opt:
-            if list(opt.get("names", self._on.names)) != list(self._on.names):
-                raise ValueError("PgmTrainStep.load_state_dict: the optimiser state belongs to other parameters")
-            self.m.copy_(opt["exp_avg"])
-            self.v.copy_(opt["exp_avg_sq"])
-            self.state.copy_(opt["state"])
+            self.tail.load_flat_optimizer_state(opt, self._on.names)
         self.it = int(sd.get("step", 0))

@@ -21,24 +21,12 @@ import torch
 
 from . import _lib
 from .predictor import CNN, _Head, _prep_x
+from .step_tail import NORM, Flat, HyperParams, StepTail, capture, check_warmup, flatten
 
 BN_MOMENTUM = 0.1  # nn.BatchNorm's default, what layers.py builds
 
 
-def _flatten(tensors, dev):
-    """One f32 buffer holding `tensors` back to back; each tensor's ``.data`` becomes a view of it.  Returns (flat, offsets)."""
-    flat = torch.empty(sum(t.numel() for t in tensors), dtype=torch.float32, device=dev)
-    offs, o = [], 0
-    for t in tensors:
-        k = t.numel()
-        flat[o:o + k].copy_(t.detach().reshape(-1).float())
-        t.data = flat[o:o + k].view(t.shape)
-        offs.append(o)
-        o += k
-    return flat, offs
-
-
-class _Flat:
+class _Flat(Flat):
     """The image heads of one predictor with their parameters and float buffers flattened (online model or EMA copy)."""
 
     def __init__(self, pred, dev):
@@ -53,17 +41,10 @@ class _Flat:
             names = {id(m): n for n, m in pred.named_modules()}
             prefixes = [names[id(hd.cnn)] + "." for hd in self.heads]
             self.std_fixed = float(pred.std_fixed)
-        self.names, self.params, self.bnames, self.bufs = [], [], [], []
-        for pre, hd in zip(prefixes, self.heads):
-            for n, p in hd.cnn.named_parameters():
-                self.names.append(pre + n)
-                self.params.append(p)
-            for n, b in hd.cnn.named_buffers():
-                if b.is_floating_point():
-                    self.bnames.append(pre + n)
-                    self.bufs.append(b)
-        self.flat_p, self.p_off = _flatten(self.params, dev)
-        self.flat_b, self.b_off = _flatten(self.bufs, dev)
+        super().__init__([(pre + n, p) for pre, hd in zip(prefixes, self.heads) for n, p in hd.cnn.named_parameters()], dev)
+        named = [(pre + n, b) for pre, hd in zip(prefixes, self.heads) for n, b in hd.cnn.named_buffers() if b.is_floating_point()]
+        self.bnames, self.bufs = [n for n, _ in named], [b for _, b in named]
+        self.flat_b, self.b_off = flatten(self.bufs, dev)
 
     def cnns(self):
         return [hd.cnn for hd in self.heads]
@@ -80,12 +61,12 @@ class PredictorTrainStep:
 
     def __init__(self, pred, lr=1e-4, wd=0.1, betas=(0.9, 0.999), eps=1e-8, grad_clip=200.0, lr_warmup_steps=1, ema_rate=0.999,
                  ema=True, use_graph=True, ema_update_after=100, device="cuda"):
-        if int(lr_warmup_steps) <= 0:
-            raise ValueError(f"lr_warmup_steps must be > 0 (got {lr_warmup_steps}): the linear warm-up divides by it")
+        check_warmup(lr_warmup_steps)
         self.lib = _lib.require_gpu()
         dev = self.device = torch.device(device)
-        self.lr, self.wd, self.betas, self.eps, self.grad_clip = float(lr), float(wd), (float(betas[0]), float(betas[1])), float(eps), float(grad_clip)
-        self.lr_warmup_steps, self.ema_rate, self.ema_update_after = int(lr_warmup_steps), float(ema_rate), int(ema_update_after)
+        # (no norm threshold in sup_epoch: only a non-finite norm or a NaN loss drops the step)
+        self.hp = HyperParams(float(lr), (float(betas[0]), float(betas[1])), float(eps), float(wd), float(grad_clip), float("inf"),
+                              int(lr_warmup_steps), float(ema_rate), int(ema_update_after))
         self.use_graph = use_graph
         self.ema_model = None
         if ema:
@@ -97,13 +78,11 @@ class PredictorTrainStep:
         widths = {c.width for c in self._on.cnns()}
         if len(widths) != 1:
             raise ValueError(f"PredictorTrainStep needs image heads of one width, got {sorted(widths)}")
-        n, nb = self._on.flat_p.numel(), self._on.flat_b.numel()
+        n = self._on.flat_p.numel()
         self.flat_g = torch.zeros(n, device=dev)
-        self.m = torch.zeros(n, device=dev)
-        self.v = torch.zeros(n, device=dev)
-        self._bzero = torch.zeros(3, max(nb, 1), device=dev)  # zero gradient / moments of the buffer region's EMA-only pass
-        self.state = torch.zeros(8, device=dev)
-        self.partial = torch.zeros(self.NORM_BLOCKS, device=dev)
+        self.tail = StepTail(self.lib, n, dev, self.NORM_BLOCKS)
+        self.stats = self.tail.stats  # host read of the device-side step state (one sync)
+        self.m, self.v, self.state, self.partial = self.tail.m, self.tail.v, self.tail.state, self.tail.partial
         self.out3 = torch.zeros(3, device=dev)  # [-, summed loss, 0]: what cgen_clip_decide tests for NaN
         self.res = torch.zeros(2, device=dev)   # [mean loss, gradient norm] of the last step
         self._statics, self._graphs = {}, {}
@@ -180,30 +159,17 @@ class PredictorTrainStep:
                                      None if dx is None else dx.data_ptr(), st)
         torch.mul(self.out3[1:2], 1.0 / B, out=self.res[0:1])
 
-    def _adamw(self, p, g, m, v, ema, count, lr, wd, st):
-        q = _lib.AdamwArgs()
-        q.p, q.g, q.m, q.v, q.ema, q.count = p, g, m, v, ema, count
-        q.lr, q.beta1, q.beta2, q.eps, q.wd = lr, self.betas[0], self.betas[1], self.eps, wd
-        q.ema_beta, q.warmup_steps, q.ema_update_after = self.ema_rate, self.lr_warmup_steps, self.ema_update_after
-        q.state_dev = self.state.data_ptr()
-        self.lib.adamw_ema(C.byref(q), st)
-
     def _optim(self):
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        on, g = self._on, self.flat_g
-        self.lib.sumsq_partial(g.data_ptr(), g.numel(), self.partial.data_ptr(), self.NORM_BLOCKS, st)
-        # (no norm threshold in sup_epoch: only a non-finite norm or a NaN loss drops the step)
-        self.lib.clip_decide(self.partial.data_ptr(), self.NORM_BLOCKS, self.out3.data_ptr(), self.grad_clip, float("inf"),
-                             self.state.data_ptr(), st)
-        ema = self.ema_model is not None
-        self._adamw(on.flat_p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                    self._ema.flat_p.data_ptr() if ema else None, g.numel(), self.lr, self.wd, st)
-        if ema and on.flat_b.numel():  # EMA of the running statistics: lr = wd = 0 and a zero gradient leave the buffers as they are
-            z = self._bzero
-            self._adamw(on.flat_b.data_ptr(), z[0].data_ptr(), z[1].data_ptr(), z[2].data_ptr(), self._ema.flat_b.data_ptr(),
-                        on.flat_b.numel(), 0.0, 0.0, st)
-        self.lib.step_commit(self.state.data_ptr(), st)
-        self.res[1:2].copy_(self.state[1:2])
+        on, ema = self._on, self.ema_model is not None
+        # EMA of the running statistics: lr = wd = 0 and a zero gradient leave the buffers as they are
+        stats = [(on.flat_b.data_ptr(), self._ema.flat_b.data_ptr(), on.flat_b.numel())] if ema and on.flat_b.numel() else ()
+        self.tail.run(self.hp, on.flat_p, self.flat_g, self._ema.flat_p if ema else None, self.out3,
+                      torch.cuda.current_stream(self.device).cuda_stream, ema_only=stats)
+        self.res[1:2].copy_(self.state[NORM:NORM + 1])
+
+    def _fwd_bwd_optim(self, ent):
+        self._fwd_bwd(ent)
+        self._optim()
 
     def _invalidate(self):
         self._on.invalidate()
@@ -221,17 +187,9 @@ class PredictorTrainStep:
         if graph is not None:
             graph.replay()
         else:
-            self._fwd_bwd(ent)
-            self._optim()
+            self._fwd_bwd_optim(ent)
             if self.use_graph:
-                from .train import CAPTURE_MODE
-
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode=CAPTURE_MODE):
-                    self._fwd_bwd(ent)
-                    self._optim()
-                self._graphs[key] = graph
+                self._graphs[key], _ = capture(lambda: self._fwd_bwd_optim(ent))
         self._invalidate()
         out = self.res.clone()
         return {"loss": out[0], "grad_norm": out[1]}
@@ -249,18 +207,12 @@ class PredictorTrainStep:
             grads["x"] = gx
         return self.res[0].clone(), grads
 
-    def stats(self):
-        """Host read of the device-side step state (one sync)."""
-        s = self.state.cpu().tolist()
-        return dict(grad_norm=s[1], clip_coef=s[2], skipped_last=bool(s[3]), n_skipped=int(s[4]), opt_steps=int(s[5]))
-
     def state_dict(self):
         """The reference checkpoint's keys (train_pgm.py:536-545): ``model_state_dict`` / ``ema_model_state_dict`` with the
         reference's parameter names, ``optimizer_state_dict`` (flat AdamW moments in ``named_parameters`` order of the image
         heads, and the device step state)."""
         sd = {"step": self.it, "model_state_dict": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-              "optimizer_state_dict": {"exp_avg": self.m.clone(), "exp_avg_sq": self.v.clone(), "state": self.state.clone(),
-                                       "names": list(self._on.names)}}
+              "optimizer_state_dict": self.tail.flat_optimizer_state(self._on.names)}
         if self.ema_model is not None:
             sd["ema_model_state_dict"] = {k: v.detach().clone() for k, v in self.ema_model.state_dict().items()}
         return sd
@@ -269,11 +221,6 @@ class PredictorTrainStep:
         self.model.load_state_dict(sd["model_state_dict"], strict=True)  # (copies in place: the flat views stay)
         if self.ema_model is not None and "ema_model_state_dict" in sd:
             self.ema_model.load_state_dict(sd["ema_model_state_dict"], strict=True)
-        opt = sd["optimizer_state_dict"]
-        if list(opt.get("names", self._on.names)) != list(self._on.names):
-            raise ValueError("PredictorTrainStep.load_state_dict: the optimiser state belongs to other parameters")
-        self.m.copy_(opt["exp_avg"])
-        self.v.copy_(opt["exp_avg_sq"])
-        self.state.copy_(opt["state"])
+        self.tail.load_flat_optimizer_state(sd["optimizer_state_dict"], self._on.names)
         self.it = int(sd.get("step", 0))
         self._invalidate()

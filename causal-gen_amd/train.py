@@ -11,14 +11,17 @@ Under data parallelism (one process per GPU, RCCL over xGMI) the flat f32 gradie
 buckets between the backward and the norm; ranks share the seed-driven draws and the skip flag by construction
 (the flag is a function of the all-reduced gradient and of the all-reduced nll/kl).
 """
+import contextlib
 import copy
 import math
-import ctypes as C
+import os
+from collections import namedtuple
 
 import torch
 
 from . import _lib, dp
 from .engine import StaticParents, compact_parents
+from .step_tail import CAPTURE_MODE, N_NONFINITE, N_SKIPPED, OPT_STEPS, STATE_FLOATS, HyperParams, StepTail, capture, check_warmup
 
 
 def preprocess_batch(args, batch, expand_pa=False):
@@ -44,12 +47,6 @@ def preprocess_batch(args, batch, expand_pa=False):
     if expand_pa:
         batch["pa"] = batch["pa"][..., None, None].expand(-1, -1, *(args.input_res,) * 2)
     return batch
-
-
-# hipGraph captures are THREAD-LOCAL: with a ProcessGroupNCCL alive, its watchdog thread polls events (hipEventQuery) at any
-# moment, which a capture in the default "global" mode treats as an illegal call and dies of ("operation failed due to a previous
-# error during capture") -- found by tools/dp_rccl_dryrun.py, invisible to the gloo tests
-CAPTURE_MODE = "thread_local"
 
 
 def _covers(have, want):
@@ -78,22 +75,25 @@ def linear_warmup(warmup_iters):
     return lambda it: 1.0 if it > warmup_iters else it / warmup_iters
 
 
+# A captured step: ``g1`` forward + backward (on one GPU also the optimiser tail, under data parallelism ``g2``; ``g1b``: the
+# backward pass after the overlapped form's cut), the static batch and parents (None: a device-side input) and [elbo, nll, kl]
+GraphEntry = namedtuple("GraphEntry", "g1 g2 sx spb so g1b")
+
+
 class TrainStep:
     NORM_BLOCKS = 1024
 
     def __init__(self, model, args, ema=True, use_graph=True, process_group=None, bucket_mb=32):
-        if int(args.lr_warmup_steps) <= 0:  # (before any device work) the kernel's LambdaLR(linear_warmup) divides by it
-            raise ValueError(f"lr_warmup_steps must be > 0 (got {args.lr_warmup_steps}): the linear warm-up divides by it")
+        check_warmup(args.lr_warmup_steps)
         self.model, self.args = model, args
         self.lib = _lib.require_gpu()  # (the step tail's own kernels; the model's launches go through eng.lib, the staging proxy)
         self.use_graph = use_graph
         self.pg = process_group
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
         self.bucket_elems = int(bucket_mb * (1 << 20) // 4)
-        import os as _os0
         # the data-parallel machinery (communication stream, split backward graph, bucketed all-reduce) is active with more than
         # one rank -- or, for a dry run of exactly that code through RCCL on ONE GPU, with CGEN_DP_FORCE=1 and a 1-rank group
-        self.dp = self.world > 1 or (process_group is not None and _os0.environ.get("CGEN_DP_FORCE") == "1")
+        self.dp = self.world > 1 or (process_group is not None and os.environ.get("CGEN_DP_FORCE") == "1")
         if self.dp and getattr(model, "free_bits", 0) > 0:
             self.use_graph = False  # free bits exchange per-channel KL sums inside the forward pass (vae.py): not capturable
         model.train()
@@ -101,23 +101,19 @@ class TrainStep:
         self.eng = eng
         n = eng.flat_p.numel()
         dev = eng.device
-        self.m = torch.zeros(n, device=dev)
-        self.v = torch.zeros(n, device=dev)
+        self.tail = StepTail(self.lib, n, dev, self.NORM_BLOCKS)
+        self.m, self.v, self.state, self.partial = self.tail.m, self.tail.v, self.tail.state, self.tail.partial
         self.ema_model = None
         if ema:
             self.ema_model = copy.deepcopy(model).to(dev)
             self.ema_model.requires_grad_(False)
             self.ema_model.eval()
             self.ema_flat = self.ema_model.engine().flat_p
-        self.state = torch.zeros(8, device=dev)
-        self.partial = torch.zeros(self.NORM_BLOCKS, device=dev)
         self.coefs = {}   # (B, dims) -> [device tensor (1/(B dims accu), beta/(B dims accu), beta), beta last written]
         self.coef = None
         self.ranges = None
         self.graphs = {}
         self.inputs = {}  # step_from: (data set, batch size, train, draws tap) -> data.AugmentedInput (static index / parents buffers)
-        self.static = None
-        self.out3 = None
         self.beta = float(args.beta)
         self.it = 0
         # DP: the gradient exchange either follows the backward graph (serialized: graph | bucketed all-reduce | optimiser graph)
@@ -127,10 +123,9 @@ class TrainStep:
         # through a 1-rank RCCL group (tools/dp_rccl_dryrun.py, bench.py with CGEN_DP_FORCE=1: 18.43 vs 17.39 ms), while the
         # serialized exchange of its 69.5 MB costs ~0.4 ms on an xGMI node (2 (N-1)/N x bytes at ~300 GB/s bus bandwidth).
         # CGEN_DP_OVERLAP=1 / 0 forces a form; unset, the step overlaps only when the estimated exchange exceeds that price.
-        import os as _os
-        _ov = _os.environ.get("CGEN_DP_OVERLAP")
+        _ov = os.environ.get("CGEN_DP_OVERLAP")
         if _ov is None:
-            est_s = 4.0 * n * 2.0 * max(self.world - 1, 0) / max(self.world, 1) / float(_os.environ.get("CGEN_DP_BUS_GBS", "300")) / 1e9
+            est_s = 4.0 * n * 2.0 * max(self.world - 1, 0) / max(self.world, 1) / float(os.environ.get("CGEN_DP_BUS_GBS", "300")) / 1e9
             self.dp_overlap = self.dp and est_s > 1.0e-3
             self.dp_policy = "auto: estimated exchange %.2f ms %s the ~1 ms the overlapped form costs" % (1e3 * est_s, ">" if self.dp_overlap else "<=")
         else:
@@ -140,9 +135,9 @@ class TrainStep:
             # a second background flush at the end of the DECODER's backward pass (75.5 % of the weight-gradient work of the
             # 192^2 presets; costs 0.8 % on one GPU): from there on every decoder / likelihood gradient is final -- 48 of the
             # 69.5 MB of ukbb192 -- and is exchanged under the encoder's backward pass; the graph is cut at 90 %
-            if "CGEN_WGRAD_FLUSH_FRAC" not in _os.environ:
+            if "CGEN_WGRAD_FLUSH_FRAC" not in os.environ:
                 eng.wgrad_flush_frac = [0.55, 0.755]
-            if "CGEN_DP_SPLIT_FRAC" not in _os.environ:
+            if "CGEN_DP_SPLIT_FRAC" not in os.environ:
                 eng.split_frac = 0.9
         self.comm_stream = None
         self.early_ranges = self.late_ranges = None
@@ -157,7 +152,7 @@ class TrainStep:
         # previous step, which is identical on all data-parallel ranks (all-reduced gradient + scalars feed clip_decide).
         self.overflow_backoffs, self._clean_checks, self.ls_growth_interval = 0, 0, 20
         self.ls_check_interval, self._ls_checked_it, self._ls_last_growth_it = 16, 0, None
-        self._ls_nonfinite_seen = 0.0  # state[6] (steps dropped for a non-finite norm) at the previous check
+        self._ls_nonfinite_seen = 0.0  # state[N_NONFINITE] (steps dropped for a non-finite norm) at the previous check
         self.LS_SHIFT_MIN = -16
         self.acc_g = torch.zeros(n, device=dev) if self.accu > 1 else None
 
@@ -177,7 +172,7 @@ class TrainStep:
             ent[1] = beta
         return ent[0]
 
-    def _fwd_bwd(self, x, pa, beta):
+    def _fwd_bwd(self, x, pa, beta, on_split=None):
         m, eng = self.model, self.eng
         dims = float(math.prod(x.shape[1:]))
         self.coef = self.coefs[(int(x.shape[0]), dims)][0]  # written by step() before any capture / replay
@@ -198,7 +193,11 @@ class TrainStep:
             self.lib.dgauss_nll_bwd(eng.dt, B, R, R, Cx, params.cv(), xin.cv(), self.coef.data_ptr(), 0, gparams.cv(), eng.stream)
         else:
             self.lib.dmol_nll_bwd(eng.dt, B, R, R, params.cv(), xin.cv(), self.coef.data_ptr(), 0, gparams.cv(), eng.stream)
-        eng.backward()
+        eng.on_split = on_split  # (called from inside the backward pass, where the early half of the gradient is final)
+        try:
+            eng.backward()
+        finally:
+            eng.on_split = None
         if self.acc_g is not None:
             eng.flat_axpy(eng.flat_g.data_ptr(), self.acc_g.data_ptr(), eng.flat_g.numel())
         return out3
@@ -210,31 +209,43 @@ class TrainStep:
         """Average the flat gradient (and the reported scalars, whose NaN-ness feeds the skip predicate) over the
         data-parallel ranks: a few large buckets, not 800 small tensors (xGMI rings are per-link bound)."""
         if self.dp:
-            t0 = None
-            if self.time_comm:  # (serialized form: the whole exchange is exposed)
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record()
-            dp.bucketed_allreduce_mean(self._gbuf(), self.bucket_elems, self.pg, extra=(out3,))
-            if t0 is not None:
-                t1.record()
-                self._comm_events.append((t0, t1))
+            with self._comm_timed():  # (serialized form: the whole exchange is exposed)
+                dp.bucketed_allreduce_mean(self._gbuf(), self.bucket_elems, self.pg, extra=(out3,))
 
-    # -- gradient all-reduce overlapped with the backward pass (north_star; SURVEY 5 / 8e) -------------------------
-    def _ranges_of(self, ids):
-        """Contiguous [lo, hi) ranges of the flat gradient covered by the parameters with these ids."""
+    @contextlib.contextmanager
+    def _comm_timed(self):
+        """With ``time_comm``: an event pair around the part of the gradient exchange the step waits for (``exposed_comm_ms``)."""
+        timed = self.time_comm
+        if timed:
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+        yield
+        if timed:
+            t1.record()
+            self._comm_events.append((t0, t1))
+
+    def _ranges_where(self, pred):
+        """Contiguous [lo, hi) ranges of the flat buffers covered by the parameters `pred` holds for (neighbours are joined)."""
         eng = self.eng
         rs, cur = [], None
         for p in eng.params:
             o, k = eng.p_off[id(p)], p.numel()
-            if id(p) in ids:
-                if cur is not None and cur[1] == o:
-                    cur[1] = o + k
-                else:
-                    cur = [o, o + k]
-                    rs.append(cur)
-            else:
+            if not pred(p):
                 cur = None
+            elif cur is not None and cur[1] == o:
+                cur[1] = o + k
+            else:
+                cur = [o, o + k]
+                rs.append(cur)
         return [(a, b) for a, b in rs]
+
+    # -- gradient all-reduce overlapped with the backward pass (north_star; SURVEY 5 / 8e) -------------------------
+    def _allreduce_ranges(self, ranges, works):
+        """Issue the asynchronous all-reduce (a sum) of these ranges of the flat gradient, a bucket at a time, onto `works`."""
+        g = self._gbuf()
+        for lo, hi in ranges:
+            for o in range(lo, hi, self.bucket_elems):
+                works.append(torch.distributed.all_reduce(g[o:min(hi, o + self.bucket_elems)], group=self.pg, async_op=True))
 
     def _early_launch(self):
         """Issue the all-reduce of the gradients that are already final (the decoder half, reduced by the background flush) on
@@ -244,31 +255,19 @@ class TrainStep:
             self.comm_stream = torch.cuda.Stream(self.eng.device)
         self.comm_stream.wait_stream(main)
         works = []
-        g = self._gbuf()
         with torch.cuda.stream(self.comm_stream):
-            for lo, hi in self.early_ranges:
-                for o in range(lo, hi, self.bucket_elems):
-                    works.append(torch.distributed.all_reduce(g[o:min(hi, o + self.bucket_elems)], group=self.pg, async_op=True))
+            self._allreduce_ranges(self.early_ranges, works)
         return works
 
     def _late_finish(self, out3, works):
         """All-reduce what the rest of the backward pass produced (plus the reported scalars), wait for both halves, average."""
-        g = self._gbuf()
-        t0 = None
-        if self.time_comm:
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-        for lo, hi in self.late_ranges:
-            for o in range(lo, hi, self.bucket_elems):
-                works.append(torch.distributed.all_reduce(g[o:min(hi, o + self.bucket_elems)], group=self.pg, async_op=True))
-        works.append(torch.distributed.all_reduce(out3, group=self.pg, async_op=True))
-        for w in works:
-            w.wait()
-        g.mul_(1.0 / self.world)
-        out3.mul_(1.0 / self.world)
-        if t0 is not None:
-            t1.record()
-            self._comm_events.append((t0, t1))
+        with self._comm_timed():
+            self._allreduce_ranges(self.late_ranges, works)
+            works.append(torch.distributed.all_reduce(out3, group=self.pg, async_op=True))
+            for w in works:
+                w.wait()
+            self._gbuf().mul_(1.0 / self.world)
+            out3.mul_(1.0 / self.world)
 
     def exposed_comm_ms(self):
         """Mean time per step between the end of the backward pass and the end of the gradient exchange (what the all-reduce
@@ -280,44 +279,16 @@ class TrainStep:
         self._comm_events = []
         return sum(v) / len(v)
 
-    def _used_ranges(self):
-        eng = self.eng
-        rs, cur = [], None
-        for p in eng.params:
-            o, k = eng.p_off[id(p)], p.numel()
-            used = id(p) in eng.pgrad_init and p.requires_grad
-            if used:
-                if cur is not None and cur[1] == o:
-                    cur[1] = o + k
-                else:
-                    cur = [o, o + k]
-                    rs.append(cur)
-            else:
-                cur = None
-        return [(a, b) for a, b in rs]
-
     def _optim(self, out3):
         eng, a = self.eng, self.args
-        st = eng.stream
-        gbuf = self._gbuf()
-        self.lib.sumsq_partial(gbuf.data_ptr(), gbuf.numel(), self.partial.data_ptr(), self.NORM_BLOCKS, st)
-        self.lib.clip_decide(self.partial.data_ptr(), self.NORM_BLOCKS, out3.data_ptr(), float(a.grad_clip), float(a.grad_skip),
-                             self.state.data_ptr(), st)
-        if self.ranges is None:
-            self.ranges = self._used_ranges()
-        for (lo, hi) in self.ranges:
-            q = _lib.AdamwArgs()
-            q.p = eng.flat_p.data_ptr() + 4 * lo
-            q.g = gbuf.data_ptr() + 4 * lo
-            q.m = self.m.data_ptr() + 4 * lo
-            q.v = self.v.data_ptr() + 4 * lo
-            q.ema = self.ema_flat.data_ptr() + 4 * lo if self.ema_model is not None else None
-            q.count = hi - lo
-            q.lr, q.beta1, q.beta2, q.eps, q.wd = float(a.lr), float(a.betas[0]), float(a.betas[1]), 1e-8, float(a.wd)
-            q.ema_beta, q.warmup_steps, q.ema_update_after = float(a.ema_rate), int(a.lr_warmup_steps), 100
-            q.state_dev = self.state.data_ptr()
-            self.lib.adamw_ema(C.byref(q), st)
-        self.lib.step_commit(self.state.data_ptr(), st)
+        eng.stream = torch.cuda.current_stream(eng.device).cuda_stream  # (inside a capture: the capturing stream)
+        # (read from `args` at every eager step: an eager run may move them between steps; a captured step has them baked in)
+        hp = HyperParams(float(a.lr), (float(a.betas[0]), float(a.betas[1])), 1e-8, float(a.wd), float(a.grad_clip), float(a.grad_skip),
+                         int(a.lr_warmup_steps), float(a.ema_rate), 100)
+        if self.ranges is None:  # the parameters the backward pass writes a gradient for: the others keep weights and moments
+            self.ranges = self._ranges_where(lambda p: id(p) in eng.pgrad_init and p.requires_grad)
+        self.tail.run(hp, eng.flat_p, self._gbuf(), self.ema_flat if self.ema_model is not None else None, out3, eng.stream,
+                      ranges=self.ranges)
         if self.acc_g is not None:  # model.zero_grad() of trainer.py:87
             eng.flat_axpy(None, self.acc_g.data_ptr(), self.acc_g.numel(), alpha=0.0, accumulate=False)
 
@@ -327,7 +298,7 @@ class TrainStep:
         works, fired = [], []
         if overlap:
             def at_split():
-                now = self._ranges_of(self.eng.early_final)
+                now = self._ranges_where(lambda p: id(p) in self.eng.early_final)
                 if self.early_ranges is None:  # first step: which flat ranges are final here, and which come later
                     self.early_ranges = now
                 # the ranges are fixed by the FIRST tape; another tape (other batch shape / drop_cond outcome) may cut at a
@@ -338,32 +309,22 @@ class TrainStep:
                     works.extend(self._early_launch())
                     fired.append(True)
             self._early_ok = True
-            self.eng.on_split = at_split
-        try:
-            out3 = self._fwd_bwd(x, pa, beta)
-        finally:
-            self.eng.on_split = None
+        out3 = self._fwd_bwd(x, pa, beta, at_split if overlap else None)
         self.eng.stream = torch.cuda.current_stream(self.eng.device).cuda_stream
         if do_step:
-            if overlap and not self._early_ok:
-                self._allreduce(out3)
-            elif overlap:
+            if overlap and self._early_ok:
                 if self.early_ranges is None:
                     self.early_ranges = []  # (the split mark was never reached: tiny model) -> everything is "late"
                 elif not fired:
                     works.extend(self._early_launch())  # (a step without the background flush, e.g. the profiled one: exchange that half now)
-                if self.late_ranges is None:
-                    used = self._used_or_all_ranges()
-                    self.late_ranges = _subtract_ranges(used, self.early_ranges)
+                if self.late_ranges is None:  # (the rest of the WHOLE buffer, the slots of unused parameters included)
+                    self.late_ranges = _subtract_ranges([(0, self._gbuf().numel())], self.early_ranges)
                 self._late_finish(out3, works)
             else:
                 self._allreduce(out3)
             self._optim(out3)
             self._mark_weights_written()
         return out3
-
-    def _used_or_all_ranges(self):
-        return [(0, self._gbuf().numel())]
 
     def _mark_weights_written(self):
         """The fused AdamW / EMA kernel writes both flat parameter buffers through raw pointers, which torch's version
@@ -406,6 +367,17 @@ class TrainStep:
         do_step = (self.it - 1) % self.accu == 0
         if not self.use_graph:
             return self._eager(x, pa, beta, do_step)
+        key = self._graph_key(x, pa, do_step)
+        ent = self.graphs.get(key)
+        self._coef_for(x, beta)
+        if ent is None:
+            out = self._eager(x, pa, beta, do_step)  # eager warm-up: sizes the arena, builds the tables
+            self.graphs[key] = self._capture(x, pa, beta, do_step)
+            return out
+        return self._replay(ent, x, pa, do_step)
+
+    def _graph_key(self, x, pa, do_step):
+        """What a captured step is valid for.  Draws ``drop_cond`` on the host and pins the outcome for this step's launches."""
         m = self.model
         drop = (1, 1)
         if m.cond_prior:  # host draw (shared across DP ranks through the common seed), one graph per outcome
@@ -413,74 +385,70 @@ class TrainStep:
             m.decoder.__dict__["drop_cond"] = lambda d=drop: d
         # (beta is device data: the warm-up schedule replays the same graph; virtual and materialised parents are different graphs)
         static = hasattr(x, "emit")  # a device-side input (step_from): its buffers are static already, its identity keys the graph
-        key = (tuple(x.shape), x.dtype, drop, do_step, tuple(pa.shape), compact_parents(pa) is not None, x.key if static else None)
-        ent = self.graphs.get(key)
-        self._coef_for(x, beta)
-        if ent is None:
-            out = self._eager(x, pa, beta, do_step)  # eager warm-up: sizes the arena, builds the tables
-            if static:
-                sx, spb, sp = x, None, pa
-            else:
-                sx, spb = x.clone(), StaticParents(pa)
-                sp = spb.t
-            torch.cuda.synchronize()
-            # NCCL inside a captured graph is avoided: under DP the step is graphs around eager all-reduces.  With overlap the
-            # backward graph is cut where the decoder half of the gradient is final (engine.on_split): graph A | all-reduce of
-            # that half on the communication stream | graph B (rest of the backward pass) | all-reduce of the rest | graph C.
-            overlap = self.dp_overlap and do_step and self.acc_g is None and bool(self.early_ranges) and self._early_ok
-            g1, g1b = torch.cuda.CUDAGraph(), None
-            if overlap:
-                g1b = torch.cuda.CUDAGraph()
-                cap = torch.cuda.Stream(self.eng.device)
-                cap.wait_stream(torch.cuda.current_stream(self.eng.device))
-                fired = []
+        return (tuple(x.shape), x.dtype, drop, do_step, tuple(pa.shape), compact_parents(pa) is not None, x.key if static else None)
 
-                def at_split():
-                    g1.capture_end()
-                    g1b.capture_begin(pool=g1.pool(), capture_error_mode=CAPTURE_MODE)
-                    fired.append(True)
+    def _capture(self, x, pa, beta, do_step):
+        """The step just run eagerly, captured on static copies of its inputs.  NCCL inside a captured graph is avoided: under DP
+        the step is graphs around eager all-reduces (``_replay``)."""
+        if hasattr(x, "emit"):
+            sx, spb, sp = x, None, pa
+        else:
+            sx, spb = x.clone(), StaticParents(pa)
+            sp = spb.t
 
-                with torch.cuda.stream(cap):
-                    g1.capture_begin(capture_error_mode=CAPTURE_MODE)
-                    self.eng.on_split = at_split
-                    try:
-                        so = self._fwd_bwd(sx, sp, beta)
-                    finally:
-                        self.eng.on_split = None
-                    (g1b if fired else g1).capture_end()
-                torch.cuda.current_stream(self.eng.device).wait_stream(cap)
-                if not fired:
-                    g1b = None
-            else:
-                with torch.cuda.graph(g1, capture_error_mode=CAPTURE_MODE):
-                    so = self._fwd_bwd(sx, sp, beta)
-                    if not self.dp and do_step:
-                        self.eng.stream = torch.cuda.current_stream(self.eng.device).cuda_stream
-                        self._optim(so)
-            g2 = None
-            if self.dp and do_step:
-                g2 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g2, capture_error_mode=CAPTURE_MODE):
-                    self.eng.stream = torch.cuda.current_stream(self.eng.device).cuda_stream
-                    self._optim(so)
-            self.graphs[key] = (g1, g2, sx, spb, so, g1b)
-            return out
-        g1, g2, sx, spb, so, g1b = ent
-        if not static and sx.data_ptr() != x.data_ptr():
-            sx.copy_(x, non_blocking=True)
-            spb.load(pa)
-        g1.replay()
-        if g1b is not None:
+        def fwd_bwd():
+            so = self._fwd_bwd(sx, sp, beta)
+            if not self.dp and do_step:
+                self._optim(so)
+            return so
+
+        g1b = g2 = None
+        if self.dp_overlap and do_step and self.acc_g is None and bool(self.early_ranges) and self._early_ok:
+            g1, g1b, so = self._capture_split(sx, sp, beta)
+        else:
+            g1, so = capture(fwd_bwd)
+        if self.dp and do_step:
+            g2, _ = capture(lambda: self._optim(so))
+        return GraphEntry(g1, g2, sx, spb, so, g1b)
+
+    def _capture_split(self, sx, sp, beta):
+        """Forward + backward captured as TWO graphs, cut where the decoder half of the gradient is final (engine.on_split):
+        graph A | all-reduce of that half on the communication stream | graph B (rest of the backward pass) | all-reduce of the
+        rest | the optimiser's graph.  Returns (A, B or None when the cut was never reached, static out3)."""
+        torch.cuda.synchronize()
+        g1, g1b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        cap = torch.cuda.Stream(self.eng.device)
+        cap.wait_stream(torch.cuda.current_stream(self.eng.device))
+        fired = []
+
+        def at_split():
+            g1.capture_end()
+            g1b.capture_begin(pool=g1.pool(), capture_error_mode=CAPTURE_MODE)
+            fired.append(True)
+
+        with torch.cuda.stream(cap):
+            g1.capture_begin(capture_error_mode=CAPTURE_MODE)
+            so = self._fwd_bwd(sx, sp, beta, at_split)
+            (g1b if fired else g1).capture_end()
+        torch.cuda.current_stream(self.eng.device).wait_stream(cap)
+        return g1, g1b if fired else None, so
+
+    def _replay(self, ent, x, pa, do_step):
+        if ent.spb is not None and ent.sx.data_ptr() != x.data_ptr():
+            ent.sx.copy_(x, non_blocking=True)
+            ent.spb.load(pa)
+        ent.g1.replay()
+        if ent.g1b is not None:
             works = self._early_launch()
-            g1b.replay()
-            self._late_finish(so, works)
-            g2.replay()
-        elif g2 is not None:
-            self._allreduce(so)
-            g2.replay()
+            ent.g1b.replay()
+            self._late_finish(ent.so, works)
+            ent.g2.replay()
+        elif ent.g2 is not None:
+            self._allreduce(ent.so)
+            ent.g2.replay()
         if do_step:
             self._mark_weights_written()
-        return so
+        return ent.so
 
     # -- checkpoint / resume (trainer.py:154-165, main.py:75-90) -----------------------------------------------
     def state_dict(self):
@@ -489,7 +457,7 @@ class TrainStep:
         plus this harness's own counters under ``"cgen"``."""
         eng, a = self.eng, self.args
         st = self.state.cpu()
-        steps = float(st[5])
+        steps = float(st[OPT_STEPS])
         state = {}
         for i, p in enumerate(eng.params):
             o, k = eng.p_off[id(p)], p.numel()
@@ -499,7 +467,7 @@ class TrainStep:
                  "eps": 1e-8, "weight_decay": float(a.wd), "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
                  "differentiable": False, "fused": None, "initial_lr": float(a.lr), "params": list(range(len(eng.params)))}
         return {"state": state, "param_groups": [group],
-                "cgen": {"it": self.it, "opt_steps": int(steps), "n_skipped": int(st[4]),
+                "cgen": {"it": self.it, "opt_steps": int(steps), "n_skipped": int(st[N_SKIPPED]),
                          "loss_scale_shift": int(self.eng.loss_scale_shift), "overflow_backoffs": int(self.overflow_backoffs),
                          "ls_growth_interval": int(self.ls_growth_interval),
                          "acc_g": None if self.acc_g is None else self.acc_g.clone()}}
@@ -507,7 +475,7 @@ class TrainStep:
     def scheduler_state_dict(self):
         """``LambdaLR.state_dict()`` of the reference's warm-up scheduler (train_setup.py:49-51): one step per successful
         optimiser step."""
-        steps = int(self.state[5].item())
+        steps = int(self.state[OPT_STEPS].item())
         a = self.args
         lr = float(a.lr) * linear_warmup(int(a.lr_warmup_steps))(steps)
         return {"base_lrs": [float(a.lr)], "last_epoch": steps, "_step_count": steps + 1, "_get_lr_called_within_step": False,
@@ -529,13 +497,13 @@ class TrainStep:
         extra = sd.get("cgen") or {}
         if "opt_steps" in extra:
             steps = float(extra["opt_steps"])
-        st = torch.zeros(8)
-        st[5] = 0.0 if steps is None else steps
-        st[4] = float(extra.get("n_skipped", 0))
+        st = torch.zeros(STATE_FLOATS)
+        st[OPT_STEPS] = 0.0 if steps is None else steps
+        st[N_SKIPPED] = float(extra.get("n_skipped", 0))
         self.state.copy_(st)
-        self.it = int(extra.get("it", st[5]))
+        self.it = int(extra.get("it", st[OPT_STEPS]))
         self._ls_checked_it, self._clean_checks, self._ls_last_growth_it = self.it, 0, None
-        self._ls_nonfinite_seen = 0.0  # (state[6] restarts at zero with the state vector)
+        self._ls_nonfinite_seen = 0.0  # (state[N_NONFINITE] restarts at zero with the state vector)
         self.overflow_backoffs = int(extra.get("overflow_backoffs", 0))
         self.ls_growth_interval = int(extra.get("ls_growth_interval", self.ls_growth_interval))
         shift = max(self.LS_SHIFT_MIN, min(0, int(extra.get("loss_scale_shift", 0))))
@@ -554,11 +522,11 @@ class TrainStep:
             return
         self._ls_checked_it = self.it
         s = self.state.cpu().tolist()
-        # decided from a COUNTER, not from a sample of the last step: state[6] counts the steps dropped for a non-finite
+        # decided from a COUNTER, not from a sample of the last step: state[N_NONFINITE] counts the steps dropped for a non-finite
         # norm; any of the ls_check_interval steps since the previous check having overflowed backs the scale off, and a check only
         # counts as clean when none did
-        overflow = s[6] > self._ls_nonfinite_seen
-        self._ls_nonfinite_seen = s[6]
+        overflow = s[N_NONFINITE] > self._ls_nonfinite_seen
+        self._ls_nonfinite_seen = s[N_NONFINITE]
         if overflow:
             if self.eng.loss_scale_shift > self.LS_SHIFT_MIN:
                 self._rescale(-1)
@@ -578,8 +546,7 @@ class TrainStep:
         """Host read of the device-side step state (one sync; call every N steps, not every step).  Read-only: the f16
         loss-scale back-off lives in step() (`_loss_scale_check`); `overflow_backoffs` counts the halvings so far,
         `loss_scale_shift` is the current log2 offset from the rule's value."""
-        s = self.state.cpu().tolist()
-        out = dict(grad_norm=s[1], clip_coef=s[2], skipped_last=bool(s[3]), n_skipped=int(s[4]), opt_steps=int(s[5]))
+        out = self.tail.stats()
         if self.eng.dtype_name != "f32":
             out.update(loss_scale=self.eng.loss_scale, loss_scale_shift=self.eng.loss_scale_shift, overflow_backoffs=self.overflow_backoffs)
         return out

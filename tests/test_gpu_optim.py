@@ -1,4 +1,5 @@
-"""The optimiser tail (csrc/optim.hip: sumsq_partial -> clip_decide -> adamw_ema -> step_commit) driven directly on flat f32
+"""The optimiser tail (csrc/optim.hip: sumsq_partial -> clip_decide -> adamw_ema -> step_commit) driven through step_tail.StepTail
+(what the training steps run; test_count_zero and the direct side of test_step_tail_issues_the_direct_sequence call _lib) on flat f32
 buffers with a hand-set state vector, against an f64 restatement built from oracle/train_ref (linear_warmup, clip_coef, ema_decay
 and the AdamW lines of RefTrainer.apply_grads), and over a 120-step sequence against RefTrainer.apply_grads itself.
 
@@ -45,27 +46,62 @@ def lib():
     return _lib.require_gpu()
 
 
-def run_tail(lib, b, state, hp, nblk=1024, out3=None, ranges=None, ema=True):
-    """One optimiser step as TrainStep._optim issues it.  b: dict of flat f32 cuda buffers p, g, m, v, ema."""
+def run_tail(lib, b, state, hp, nblk=1024, out3=None, ranges=None, ema=True, ema_only=()):
+    """One optimiser step through step_tail.StepTail, the code the three training steps run, on the caller's moments and state
+    vector.  b: dict of flat f32 cuda buffers p, g, m, v, ema."""
+    from causal_gen_amd.step_tail import HyperParams, StepTail
+
+    tail = StepTail(lib, 0, "cuda", nblk)
+    tail.m, tail.v, tail.state = b["m"], b["v"], state
+    tail.partial.fill_(NAN)
+    tail.run(HyperParams(hp.lr, (hp.betas[0], hp.betas[1]), 1e-8, hp.wd, float(hp.grad_clip), float(hp.grad_skip), hp.lr_warmup_steps,
+                         hp.ema_rate, EMA_AFTER),
+             b["p"], b["g"], b["ema"] if ema else None, out3, torch.cuda.current_stream().cuda_stream, ranges=ranges, ema_only=ema_only)
+    torch.cuda.synchronize()
+
+
+def test_step_tail_issues_the_direct_sequence(lib):
+    """StepTail.run against the same launches issued here through _lib on cloned buffers, one element past a 256-thread block:
+    two ranges with a gap and an EMA-only region.  Every buffer the tail writes is bit-identical, the gap is untouched."""
     from causal_gen_amd import _lib
 
+    count, ranges, nb = 257, [(0, 100), (130, 257)], 33
+    b0 = _bufs(count, 41, 5.0)
+    hp = _hp(clip=0.5 * float(b0["g"].double().norm()))  # clipped, not skipped
+    gen = torch.Generator(device="cuda").manual_seed(42)
+    pb0, eb0 = torch.randn(nb, generator=gen, device="cuda"), torch.randn(nb, generator=gen, device="cuda")
+    out3 = torch.tensor([1.0, 2.0, 3.0], device="cuda")
+
+    b, state, pb, eb = {k: v.clone() for k, v in b0.items()}, _state(103), pb0.clone(), eb0.clone()
+    run_tail(lib, b, state, hp, out3=out3, ranges=ranges, ema_only=[(pb.data_ptr(), eb.data_ptr(), nb)])
+
+    d, dstate, dpb, deb = {k: v.clone() for k, v in b0.items()}, _state(103), pb0.clone(), eb0.clone()
     st = torch.cuda.current_stream().cuda_stream
-    count = b["g"].numel()
-    partial = torch.full((nblk,), NAN, device="cuda")
-    lib.sumsq_partial(b["g"].data_ptr(), count, partial.data_ptr(), nblk, st)
-    lib.clip_decide(partial.data_ptr(), nblk, None if out3 is None else out3.data_ptr(), float(hp.grad_clip), float(hp.grad_skip),
-                    state.data_ptr(), st)
-    for lo, hi in ranges or [(0, count)]:
+    partial, zero = torch.full((1024,), NAN, device="cuda"), torch.zeros(3, nb, device="cuda")
+
+    def adamw(p, g, m, v, e, n, lr, wd):
         q = _lib.AdamwArgs()
-        q.p, q.g, q.m, q.v = (b[k].data_ptr() + 4 * lo for k in "pgmv")
-        q.ema = b["ema"].data_ptr() + 4 * lo if ema else None
-        q.count = hi - lo
-        q.lr, q.beta1, q.beta2, q.eps, q.wd = hp.lr, hp.betas[0], hp.betas[1], 1e-8, hp.wd
-        q.ema_beta, q.warmup_steps, q.ema_update_after = hp.ema_rate, hp.lr_warmup_steps, EMA_AFTER
-        q.state_dev = state.data_ptr()
+        q.p, q.g, q.m, q.v, q.ema, q.count = p, g, m, v, e, n
+        q.lr, q.beta1, q.beta2, q.eps, q.wd = lr, hp.betas[0], hp.betas[1], 1e-8, wd
+        q.ema_beta, q.warmup_steps, q.ema_update_after, q.state_dev = hp.ema_rate, hp.lr_warmup_steps, EMA_AFTER, dstate.data_ptr()
         lib.adamw_ema(C.byref(q), st)
-    lib.step_commit(state.data_ptr(), st)
+
+    lib.sumsq_partial(d["g"].data_ptr(), count, partial.data_ptr(), 1024, st)
+    lib.clip_decide(partial.data_ptr(), 1024, out3.data_ptr(), float(hp.grad_clip), float(hp.grad_skip), dstate.data_ptr(), st)
+    for lo, hi in ranges:
+        adamw(*(d[k].data_ptr() + 4 * lo for k in ("p", "g", "m", "v", "ema")), hi - lo, hp.lr, hp.wd)
+    adamw(dpb.data_ptr(), zero[0].data_ptr(), zero[1].data_ptr(), zero[2].data_ptr(), deb.data_ptr(), nb, 0.0, 0.0)
+    lib.step_commit(dstate.data_ptr(), st)
     torch.cuda.synchronize()
+
+    for k in ("p", "m", "v", "ema"):
+        assert torch.equal(_bits(b[k]), _bits(d[k])), k
+        assert torch.equal(_bits(b[k][100:130]), _bits(b0[k][100:130])), k  # the gap
+        assert not torch.equal(_bits(b[k][:100]), _bits(b0[k][:100])) and not torch.equal(_bits(b[k][130:]), _bits(b0[k][130:])), k
+    assert torch.equal(_bits(state), _bits(dstate)) and float(state[5]) == 104.0 and float(state[3]) == 0.0 and float(state[2]) < 1.0
+    assert torch.equal(_bits(eb), _bits(deb)) and not torch.equal(_bits(eb), _bits(eb0))  # the statistics' EMA moved ...
+    assert torch.equal(_bits(pb), _bits(dpb)) and torch.equal(_bits(pb), _bits(pb0))  # ... the statistics did not (lr = wd = 0, g = 0)
+    assert not zero.any()
 
 
 def ref_update(b0, t0, c, hp):
