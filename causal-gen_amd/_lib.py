@@ -35,7 +35,8 @@ class Block3Out(C.Structure):
 class Block3Args(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("nseg", C.c_int32),
                 ("nout", C.c_int32), ("pre_act", C.c_int32), ("reserved", C.c_int32), ("seg", View * MAX_SEG),
-                ("w_a", C.c_void_p), ("bias_a", C.c_void_p), ("mid", View), ("mid_aux", View), ("o", Block3Out * 2), ("w_a16", C.c_void_p)]
+                ("w_a", C.c_void_p), ("bias_a", C.c_void_p), ("mid", View), ("mid_aux", View), ("o", Block3Out * 2), ("w_a16", C.c_void_p),
+                ("w_proj", C.c_void_p), ("bias_proj", C.c_void_p), ("proj_krow", C.c_int32), ("pool", C.c_int32)]  # (the down Block: zero = absent)
 
 
 class Block4Args(C.Structure):

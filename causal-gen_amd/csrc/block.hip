@@ -68,6 +68,11 @@ struct B3P {
   // row-streaming instance (blk3r): strips of 32 columns x r_rs rows
   int rows, r_rs, r_sx, r_sy, r_res_tile, r_pad;
   const char* wA16;  // 16-row image of conv1 ([tap][chunk][lane][8]; cgen_weight_prep modes 6 / 7)
+  // ... of a down Block (cgen_block3_args.w_proj): the 1x1 projection's row-major image (forward: mode 0, data gradient: mode 1; row
+  // stride r_pkrow elements) and bias; r_pool = 2: the epilogue averages 2x2 outputs and o[0].out is the pooled tensor
+  const char* wP;
+  const float* biasP;
+  int r_pkrow, r_pool;
   const char* wA;   // phase-A fragment image [32-row block][chunk][channel half 0..1][tap 0..8][lane][8]
   const float* biasA;
   BV3 mid, mid_aux;  // mid: written (interior pixels): forward t (pre-activation), backward g_t; mid_aux: backward mask source t
@@ -1186,6 +1191,21 @@ __global__ __launch_bounds__(64 * B3S_NW, 4) void blk3s_pair_kernel(B3P pa, B3P 
 //   * phase B: a wave owns one output row of 32 pixels for one 32-channel pair (32x32x16, weights in registers), epilogue from the
 //     accumulators: bias, residual from the input ring / mask and accumulated gradient from HBM, two 16-byte stores per lane.
 // Two barriers per band.  Forward and data gradient (one output) share the body like the tile instance.
+// PROJ = 1: the encoder's DOWN Block (vae.py:70-84: out = width_proj(x) + conv(x), avg_pool2d(out, 2)) in this launch.
+//   * phase B continues with the 1x1 projection of the band's own pixels: its B operand is the RAW centre pixel of the input ring (the
+//     address RES = 1 reads the residual from), its A operand 16-row fragments read at the top of the launch straight from the
+//     projection's row-major image.  It repeats conv_px's arithmetic -- v_mfma_f32_16x16x32 over 32 channels per step, the bias as the
+//     initial value -- so that the term has the BITS of the separate launch; the 16 x 16 result tiles reach phase B's layout (lane =
+//     pixel, 16 consecutive channels) through a page of LDS per wave (PJT; same wave, no barrier).  Forward: rn16(W_p x + b_p) replaces
+//     the residual.  Data gradient: the ring holds g = grad(out); the Block's own result is rounded to binary16 BEHIND the ReLU mask
+//     of the conv branch (it was stored) and W_p^T g is added to it in f32, as the projection's launch accumulated onto it.
+//   * forward, pooling: a wave's row of rounded outputs goes into an exchange buffer of its own region of LDS ([4 rows][32 pixels]
+//     [Co channels + one 16-byte pad group], behind the DMA overhang page SCR), a THIRD barrier, then waves 0-3 average 2x2 in f32
+//     (avgpool_fwd's order) and write the two pooled rows of the band with 16-byte stores.  Neither the un-pooled output nor the
+//     projected residual reaches HBM.  Both buffers are written by ds_write and read by ds_read only: no LDS-DMA request, in flight or
+//     not, targets them (ring groups and SCR lie below them), so the hand-counted waits have nothing to say about it; band k + 1's
+//     writes come after two barriers every reader of band k has passed with lgkmcnt(0).  The band's counted wait still sits in
+//     front of the first store of the band (the bottleneck rows'); the pooled stores are younger.
 #define B3R_NW 8
 #define B3R_XC 36
 #define B3R_MC 34
@@ -1194,21 +1214,31 @@ __global__ __launch_bounds__(64 * B3S_NW, 4) void blk3s_pair_kernel(B3P pa, B3P 
 constexpr int b3r_grpb(int nch) { return ((4 * B3R_XC * (nch * 4 + 1) * 16 + 1023) / 1024) * 1024; }  // one ring group: four input rows, whole DMA instructions
 constexpr int b3r_mrowb(int nb) { return B3R_MC * ((nb & 1) ? nb : nb + 1) * 16; }
 constexpr size_t b3r_lds(int nch, int nb) { return (size_t)B3R_NG * b3r_grpb(nch) + (size_t)B3R_MR * b3r_mrowb(nb) + 1024; }
+#define B3R_PJTS 144                // PROJ: bytes per pixel of a wave's layout-exchange page (32 f32 + a pad group: an odd number of 16-byte groups)
+#define B3R_PJTB (32 * B3R_PJTS)
+constexpr size_t b3r_exb(int co) { return (size_t)4 * 32 * (co * 2 + 16); }  // the pooling exchange buffer (PROJ, forward)
 
 // RES: where the epilogue's added operand comes from -- 0 none, 1 the input ring (forward: the residual IS the input), 2 HBM
-// (forward: another tensor; data gradient: the accumulated gradient)
-template <bool PRE, int NCH, int NB, int RES>
+// (forward: another tensor; data gradient: the accumulated gradient); PROJ: the down Block's projection (and, forward, its pooling)
+// NR: rounds of phase B per band (2: three channel pairs -- the 96-wide down Block; round r gives the wave pair (wave >> 2) + 2 r)
+template <bool PRE, int NCH, int NB, int RES, bool PROJ = false, int NR = 1>
 __global__ __launch_bounds__(64 * B3R_NW, 2) void blk3r_kernel(B3P p) {
   __builtin_amdgcn_s_setprio(3);
   constexpr int G1 = NCH * 4 + 1, XS = G1 * 16, ROWB = B3R_XC * XS, GRPB = b3r_grpb(NCH), NINST = GRPB / 1024, IPW = (NINST + B3R_NW - 1) / B3R_NW;
   constexpr int NBS = (NB & 1) ? NB : NB + 1, MS = NBS * 16, MROWB = B3R_MC * MS;
   constexpr int KA = 9 * NCH, NKB = (9 * NB + 1) / 2;
   constexpr bool AUX = !PRE;  // (the data gradient masks its output with the forward input; the forward pass has no mask)
+  constexpr bool POOL = PRE && PROJ;  // (the forward pass of a down Block: the epilogue averages 2x2 outputs)
+  constexpr int NKP = PROJ ? NCH : 1;  // K32-steps of the projection (v_mfma_f32_16x16x32, conv_px's): its K axis is the ring's channels either way
+  static_assert(!(PROJ && RES == 1) && !(POOL && RES != 0), "the projection replaces the residual");
+  static_assert(NR == 1 || POOL, "a second phase-B round exists for the pooled forward form only (no per-band epilogue loads)");
   typedef __attribute__((address_space(3))) void* lds_ptr;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const X = smem;
   char* const MID = smem + B3R_NG * GRPB;
   char* const SCR = MID + B3R_MR * MROWB;  // destination of the DMA instructions a wave issues beyond the group's last (uniform count per wave)
+  char* const PJT = SCR + 1024;            // PROJ: per wave [32 pixels][32 channels + a pad group] f32, the projection term on its way between layouts
+  char* const EXB = PJT + B3R_NW * B3R_PJTB;  // POOL: [4 rows][32 pixels][Co channels + a pad group] of rounded outputs (no DMA lands in either)
   const char* const zero = (const char*)g_b3zero;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = p.H, W = p.W, bch = p.b;
@@ -1238,15 +1268,26 @@ __global__ __launch_bounds__(64 * B3R_NW, 2) void blk3r_kernel(B3P p) {
   dma_group(1);
   dma_group(2);  // (a strip of one band never reads it: harmless rows of the image, or zeros)
   // ---- weights: all of conv1 (16-row fragments, [tap][chunk]) and this wave's pair of conv2, in registers for the launch
-  h16x8 Aw[KA], Bw[NKB];
+  h16x8 Aw[KA], Bw[NR][NKB], Pw[NR][2][NKP];
   {
     const char* wa = p.wA16 + lane * 16;
 #pragma unroll
     for (int s_ = 0; s_ < KA; ++s_) Aw[s_] = *(const h16x8*)(wa + s_ * 1024);
-    const int pair_w = min(wave >> 2, p.o[0].npb - 1);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+    const int pair_w = min((wave >> 2) + 2 * r, p.o[0].npb - 1);
     const char* wb = p.o[0].w + (size_t)pair_w * NKB * 1024 + lane * 16;
 #pragma unroll
-    for (int i = 0; i < NKB; ++i) Bw[i] = *(const h16x8*)(wb + i * 1024);
+    for (int i = 0; i < NKB; ++i) Bw[r][i] = *(const h16x8*)(wb + i * 1024);
+    if constexpr (PROJ) {  // the projection's 16-row fragments straight from its row-major image: lane = (row l & 15, channels 32 i + 8 (l >> 4) .. + 8)
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) {
+        const char* wp = p.wP + ((size_t)(pair_w * 32 + 16 * mt + (lane & 15)) * p.r_pkrow + 8 * (lane >> 4)) * 2;  // (row < Co: a multiple of 32, the host checks)
+#pragma unroll
+        for (int i = 0; i < NKP; ++i) Pw[r][mt][i] = *(const h16x8*)(wp + i * 64);
+      }
+    }
+    }
   }
   // ---- phase-A lane constants: bottleneck pixel q = 16 g + (lane & 15) of a band's new rows (34 wide), groups wave and wave + 8
   const int l16 = lane & 15, l4 = lane >> 4;
@@ -1276,25 +1317,52 @@ __global__ __launch_bounds__(64 * B3R_NW, 2) void blk3r_kernel(B3P p) {
     kty[i] = tp / 3;
     koff[i] = (pxB + tp % 3) * MS + gq * 16;
   }
-  float biasB[16];
+  float biasB[NR][16];
+  f32x4_t biasP[NR][2];  // the projection's bias (forward), rows 4 (l >> 4) .. + 4 of each 16-channel half: the accumulators' initial value, as in conv_px
 #pragma unroll
-  for (int e = 0; e < 16; ++e) biasB[e] = 0.f;
-  if (jobB && O.bias != nullptr) {
+  for (int r = 0; r < NR; ++r) {
+    const int pairR = pairB + 2 * r, ch0R = ch0 + 64 * r;
 #pragma unroll
-    for (int e = 0; e < 16; e += 4)
-      if (ch0 + e < Co) { const float4 b4 = *(const float4*)(O.bias + ch0 + e); biasB[e] = b4.x; biasB[e + 1] = b4.y; biasB[e + 2] = b4.z; biasB[e + 3] = b4.w; }
+    for (int e = 0; e < 16; ++e) biasB[r][e] = 0.f;
+    if (pairR < npb && O.bias != nullptr) {
+#pragma unroll
+      for (int e = 0; e < 16; e += 4)
+        if (ch0R + e < Co) { const float4 b4 = *(const float4*)(O.bias + ch0R + e); biasB[r][e] = b4.x; biasB[r][e + 1] = b4.y; biasB[r][e + 2] = b4.z; biasB[r][e + 3] = b4.w; }
+    }
+    biasP[r][0] = biasP[r][1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    if constexpr (POOL) {
+      if (pairR < npb && p.biasP != nullptr) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) { const float4 b4 = *(const float4*)(p.biasP + pairR * 32 + 16 * mt + 4 * l4); biasP[r][mt] = (f32x4_t){b4.x, b4.y, b4.z, b4.w}; }
+      }
+    }
   }
+  // POOL: the exchange buffer's pixel stride (an odd number of 16-byte groups: conflict-free 16-byte writes, like the ring's), and
+  // this thread's share of the band's two pooled rows: (pooled row, pooled pixel, 8-channel group)
+  const int exs = Co * 2 + 16;
+  const int pl_ng = Co >> 3, pl_pp = tid / pl_ng, pl_cg = tid - pl_pp * pl_ng, pl_px = pl_pp & 15, pl_r = pl_pp >> 4;
   // Everything loaded so far is in its registers BEFORE the band loop, as far as the compiler is concerned too: a load it still
   // considers pending inside the loop would be waited for there with a small vmcnt -- a drain of the requests in flight, per band
   B3_VMWAIT();
 #pragma unroll
   for (int s_ = 0; s_ < KA; ++s_) b3_pin(Aw[s_]);
 #pragma unroll
-  for (int i = 0; i < NKB; ++i) b3_pin(Bw[i]);
-#pragma unroll
   for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(biasA[e]));
 #pragma unroll
-  for (int e = 0; e < 16; ++e) asm volatile("" : "+v"(biasB[e]));
+  for (int r = 0; r < NR; ++r) {
+#pragma unroll
+    for (int i = 0; i < NKB; ++i) b3_pin(Bw[r][i]);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) asm volatile("" : "+v"(biasB[r][e]));
+    if constexpr (PROJ) {
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) {
+#pragma unroll
+        for (int i = 0; i < NKP; ++i) b3_pin(Pw[r][mt][i]);
+        asm volatile("" : "+v"(biasP[r][mt]));
+      }
+    }
+  }
   B3_BARRIER();
 
   // The loads of a band that are not DMA (data gradient: the forward bottleneck under this lane's two bottleneck pixels, the forward
@@ -1389,6 +1457,7 @@ __global__ __launch_bounds__(64 * B3R_NW, 2) void blk3r_kernel(B3P p) {
   // ---- prologue: the strip's first two bottleneck rows
   band_loads(Y0 - 1, 2, -1);
   phaseA(Y0 - 1, 2, 0);
+  const int ch0_ = ch0;
   for (int k = 0; k < nbands; ++k) {
     const int Y = Y0 + 4 * k, y = Y + rB;
     B3_BARRIER();            // everyone is through band k - 1: the group the next request overwrites is free, the two new rows above are visible
@@ -1396,7 +1465,10 @@ __global__ __launch_bounds__(64 * B3R_NW, 2) void blk3r_kernel(B3P p) {
     dma_group(k + 3);        // (past the strip's last group: rows nobody reads -- the count of requests stays the same)
     phaseA(Y + 1, 4, 1);     // ... group k + 2 has landed (this wave's pieces): only the request just issued may still be in flight
     B3_BARRIER();            // the band's bottleneck rows, and everyone's pieces of group k + 2
-    if (jobB) {
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int ch0 = ch0_ + 64 * r;  // (this round's channels: pair (wave >> 2) + 2 r)
+      if (!(pairB + 2 * r < npb)) continue;
       const int ox = x0 + pxB;
       const bool ev = y < Yend && ox < W;
       int rowb[3];
@@ -1404,12 +1476,12 @@ __global__ __launch_bounds__(64 * B3R_NW, 2) void blk3r_kernel(B3P p) {
       for (int ty = 0; ty < 3; ++ty) rowb[ty] = ((y - 1 + ty) & (B3R_MR - 1)) * MROWB;
       f32x16 c;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) c[e] = biasB[e];
+      for (int e = 0; e < 16; ++e) c[e] = biasB[r][e];
 #pragma unroll
       for (int i = 0; i < NKB; ++i) {
         const int rb = kty[i] == 0 ? rowb[0] : (kty[i] == 1 ? rowb[1] : rowb[2]);
         const h16x8 bq = *(const h16x8*)(MID + rb + koff[i]);
-        c = b3_mfma(Bw[i], bq, c);
+        c = b3_mfma(Bw[r][i], bq, c);
       }
       if constexpr (RES == 1) {  // the residual is the input: pixel (y, ox) of the ring, raw (the ReLU was applied to the fragments)
         const int rel = y - (Y0 - 2);
@@ -1417,9 +1489,34 @@ __global__ __launch_bounds__(64 * B3R_NW, 2) void blk3r_kernel(B3P p) {
         er[0] = *(const b3_u32x4*)rp;
         er[1] = *(const b3_u32x4*)(rp + 16);
       }
+      float cp[16];  // PROJ: the projection term of this lane's pixel and channels, f32
+      if constexpr (PROJ) {
+        // conv_px's arithmetic, so that the sum has that launch's bits: v_mfma_f32_16x16x32 over channels 32 i .. + 32 per step, the
+        // bias as the initial value.  B operand: the raw pixel (y, x0 + 16 nt + (l & 15)) of the ring, channels 32 i + 8 (l >> 4) .. + 8.
+        // Its result tile (lane = pixel l & 15, rows 4 (l >> 4) .. + 4) goes through this wave's own page of LDS into phase B's
+        // layout (lane = pixel, 16 consecutive channels): same wave, LDS operations complete in order, no barrier.
+        const int rel = y - (Y0 - 2);
+        const char* xq = X + ((rel >> 2) & (B3R_NG - 1)) * GRPB + (rel & 3) * ROWB + (l16 + 2) * XS + l4 * 16;
+        char* const tw = PJT + wave * B3R_PJTB;
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt) {
+            f32x4_t d = biasP[r][mt];
+#pragma unroll
+            for (int i = 0; i < NKP; ++i) d = mfma_h16(Pw[r][mt][i], *(const h16x8*)(xq + nt * 16 * XS + i * 64), d, 0, 0, 0);
+            *(f32x4_t*)(tw + (l16 + 16 * nt) * B3R_PJTS + (16 * mt + 4 * l4) * 4) = d;
+          }
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+          const f32x4_t d = *(const f32x4_t*)(tw + pxB * B3R_PJTS + (16 * kgB + 4 * q4) * 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) cp[4 * q4 + e] = d[e];
+        }
+      }
 #pragma unroll
       for (int q8 = 0; q8 < 2; ++q8) {
-        if (!(ev && ch0 + 8 * q8 < Co)) continue;
+        if constexpr (!POOL) { if (!(ev && ch0 + 8 * q8 < Co)) continue; }  // (POOL: every lane fills its slot of the exchange buffer)
         float u[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) u[e] = c[8 * q8 + e];
@@ -1436,7 +1533,40 @@ __global__ __launch_bounds__(64 * B3R_NW, 2) void blk3r_kernel(B3P p) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) { u[2 * e] += h_lo(w[e]); u[2 * e + 1] += h_hi(w[e]); }
         }
-        *(uint4*)((char*)O.out.p + (n * O.out.sn + y * O.out.sh + ox * O.out.sw) + ch0 * 2 + 16 * q8) = b3_pack8(u);
+        if constexpr (PROJ) {
+          // forward: the projection is rounded to binary16 (the separate launch stored it) and added like a residual.  Data gradient,
+          // behind the mask (it belongs to the conv branch): the Block's own result is rounded (it was stored) and the projection's
+          // launch accumulated onto it in f32
+          const uint4 rw = b3_pack8(PRE ? cp + 8 * q8 : u);
+          const uint32_t w[4] = {rw.x, rw.y, rw.z, rw.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if constexpr (PRE) { u[2 * e] += h_lo(w[e]); u[2 * e + 1] += h_hi(w[e]); }
+            else { u[2 * e] = h_lo(w[e]) + cp[8 * q8 + 2 * e]; u[2 * e + 1] = h_hi(w[e]) + cp[8 * q8 + 2 * e + 1]; }
+          }
+        }
+        if constexpr (POOL) *(uint4*)(EXB + (rB * 32 + pxB) * exs + ch0 * 2 + 16 * q8) = b3_pack8(u);
+        else *(uint4*)((char*)O.out.p + (n * O.out.sn + y * O.out.sh + ox * O.out.sw) + ch0 * 2 + 16 * q8) = b3_pack8(u);
+      }
+    }
+    if constexpr (POOL) {
+      B3_BARRIER();  // the band's four rows of rounded outputs
+      // H and W are even (the host checks): a pooled pixel lies inside the image and the strip with all four of its sources, or with none
+      if (pl_r < 2 && Y + 2 * pl_r + 1 < Yend && x0 + 2 * pl_px + 1 < W) {
+        const char* e0 = EXB + (2 * pl_r * 32 + 2 * pl_px) * exs + pl_cg * 16;
+        const uint4 v4[4] = {*(const uint4*)e0, *(const uint4*)(e0 + exs), *(const uint4*)(e0 + 32 * exs), *(const uint4*)(e0 + 33 * exs)};
+        float a8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a8[e] = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {  // (avgpool_fwd_body's order: (0,0) (0,1) (1,0) (1,1), f32)
+          const uint32_t w[4] = {v4[q].x, v4[q].y, v4[q].z, v4[q].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { a8[2 * e] += h_lo(w[e]); a8[2 * e + 1] += h_hi(w[e]); }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a8[e] *= 0.25f;
+        *(uint4*)((char*)O.out.p + (n * O.out.sn + ((Y >> 1) + pl_r) * O.out.sh + ((x0 >> 1) + pl_px) * O.out.sw) + pl_cg * 16) = b3_pack8(a8);
       }
     }
   }
@@ -1508,6 +1638,20 @@ static int b3_fill(const cgen_block3_args* a, B3P& p) {
     p.rows = (rows_on && !p.small && a->w_a16 && a->nseg == 1 && a->nout == 1 && (c0 == 32 || c0 == 64) && (p.b == 8 || p.b == 16)
               && (co0 == 32 || co0 == 64) && a->w >= 48 && a->h >= 16 && !a->o[0].out_rem && !a->o[0].res1_rem
               && ((uintptr_t)a->w_a16 % 16) == 0) ? 1 : 0;
+    if (a->w_proj || a->bias_proj || a->proj_krow || a->pool) {
+      // the down Block's fields: this instance or nothing.  Forward: projection AND 2x2 pooling (even sides, no other residual, the
+      // pooled tensor as the output); data gradient: the projection term alone.  The widths this instance serves anyway (32 / 64 in,
+      // bottleneck 8 / 16, 32 / 64 out) where its LDS fits: 64 -> 16 -> 64 forward does not (ring 84 KB + bottleneck ring 26 + layout
+      // pages 36 + pooling exchange 18 = 165 KB).  The 96-wide Block (a second phase-B round forward, a three-chunk ring backward)
+      // compiles to 124 - 248 bytes of scratch per lane (-DB3R_TRIAL, LABNOTES 25.4): not served.
+      const bool fwd = a->pre_act != 0;
+      if (!p.rows || !a->w_proj || ((uintptr_t)a->w_proj % 16) || ((uintptr_t)a->bias_proj % 16) || a->proj_krow < c0 || a->proj_krow % 8) return 0;
+      if (fwd ? !(a->pool == 2 && a->h % 2 == 0 && a->w % 2 == 0 && !a->o[0].res1.p && !a->mid_aux.p)
+              : !(a->pool == 0 && !a->bias_proj && a->mid_aux.p)) return 0;
+      if (b3r_lds(c0 / 32, p.b / 8) + (size_t)B3R_NW * B3R_PJTB + (fwd ? b3r_exb(co0) : 0) > 160 * 1024) return 0;
+      if (fwd && !b3_view(a->o[0].out, a->n, a->h / 2, a->w / 2, p.o[0].out)) return 0;
+      p.wP = (const char*)a->w_proj; p.biasP = a->bias_proj; p.r_pkrow = a->proj_krow; p.r_pool = a->pool;
+    }
     if (p.rows) {
       p.wA16 = (const char*)a->w_a16;
       p.r_sx = ceil_div(p.W, 32);
@@ -1678,6 +1822,12 @@ static int b3_pair_plan(const cgen_block3_args* a, const cgen_block3_args* b, B3
   return 1;
 }
 
+#ifdef B3R_TRIAL  // -DB3R_TRIAL: instances of the down Block that are NOT served, compiled for their resource usage only (LABNOTES 25.4)
+template __global__ void blk3r_kernel<true, 2, 2, 0, true, 2>(B3P);   // 64 -> 16 -> 96 forward: three pairs, two phase-B rounds
+template __global__ void blk3r_kernel<false, 3, 2, 0, true, 1>(B3P);  // its data gradient: 96 -> 16 -> 64, three-chunk ring
+template __global__ void blk3r_kernel<false, 3, 2, 2, true, 1>(B3P);
+#endif
+
 }  // namespace cgen
 
 using namespace cgen;
@@ -1719,14 +1869,18 @@ extern "C" int cgen_block3(const cgen_block3_args* a, cgen_stream_t stream) {
   CGEN_REQUIRE((a->pre_act != 0) == (a->mid_aux.p == nullptr), "cgen_block3: pre_act = 1 is the forward pass (no mid_aux), pre_act = 0 the data gradient (mid_aux = the forward mid)");
   if (p.rows) {
     const int nch = a->seg[0].c / 32, nb = p.b / 8;
-    const size_t lds = b3r_lds(nch, nb);
-#define B3R_LAUNCH(PRE_, NCH_, NB_, RES_) do { (void)hipFuncSetAttribute((const void*)blk3r_kernel<PRE_, NCH_, NB_, RES_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((blk3r_kernel<PRE_, NCH_, NB_, RES_>), dim3(p.ntiles), dim3(64 * B3R_NW), lds, (hipStream_t)stream, p); } while (0)
+    const size_t lds = b3r_lds(nch, nb) + (p.wP ? (size_t)B3R_NW * B3R_PJTB : 0) + (p.r_pool ? b3r_exb(p.o[0].Co) : 0);
+#define B3R_LAUNCH(PRE_, NCH_, NB_, RES_, ...) do { (void)hipFuncSetAttribute((const void*)blk3r_kernel<PRE_, NCH_, NB_, RES_, ##__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+    hipLaunchKernelGGL((blk3r_kernel<PRE_, NCH_, NB_, RES_, ##__VA_ARGS__>), dim3(p.ntiles), dim3(64 * B3R_NW), lds, (hipStream_t)stream, p); } while (0)
 #define B3R_RES(PRE_, NCH_, NB_) do { if (res_mode == 0) B3R_LAUNCH(PRE_, NCH_, NB_, 0); else if (res_mode == 1) B3R_LAUNCH(PRE_, NCH_, NB_, 1); else B3R_LAUNCH(PRE_, NCH_, NB_, 2); } while (0)
 #define B3R_RES_BWD(NCH_, NB_) do { if (res_mode == 0) B3R_LAUNCH(false, NCH_, NB_, 0); else B3R_LAUNCH(false, NCH_, NB_, 2); } while (0)
     const int res_mode = !a->o[0].res1.p ? 0 : (p.r_res_tile ? 1 : 2);
-    if (a->pre_act) { if (nch == 1) { if (nb == 1) B3R_RES(true, 1, 1); else B3R_RES(true, 1, 2); } else { if (nb == 1) B3R_RES(true, 2, 1); else B3R_RES(true, 2, 2); } }
+#define B3R_DOWN(NCH_, NB_) do { if (a->pre_act) B3R_LAUNCH(true, NCH_, NB_, 0, true); else if (res_mode == 0) B3R_LAUNCH(false, NCH_, NB_, 0, true); else B3R_LAUNCH(false, NCH_, NB_, 2, true); } while (0)
+    if (p.wP) {  // the down Block
+      if (nch == 1) { if (nb == 1) B3R_DOWN(1, 1); else B3R_DOWN(1, 2); } else { if (nb == 1) B3R_DOWN(2, 1); else B3R_DOWN(2, 2); }
+    } else if (a->pre_act) { if (nch == 1) { if (nb == 1) B3R_RES(true, 1, 1); else B3R_RES(true, 1, 2); } else { if (nb == 1) B3R_RES(true, 2, 1); else B3R_RES(true, 2, 2); } }
     else { if (nch == 1) { if (nb == 1) B3R_RES_BWD(1, 1); else B3R_RES_BWD(1, 2); } else { if (nb == 1) B3R_RES_BWD(2, 1); else B3R_RES_BWD(2, 2); } }
+#undef B3R_DOWN
 #undef B3R_RES
 #undef B3R_RES_BWD
 #undef B3R_LAUNCH

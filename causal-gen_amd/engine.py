@@ -373,6 +373,10 @@ class Engine(WgradMixin):
         # the row-streaming instance (96x96 / 192x192 Blocks, csrc/block.hip blk3r): CGEN_BLK3R=0 off; where it serves a shape the side
         # policy below (blk3_res) does not apply
         self.blk3_rows = int(os.environ.get("CGEN_BLK3R", "1"))
+        # the encoder's down Block on that instance (width_proj, the residual add and avg_pool2d(2) inside the Block's launch; the
+        # projection's data gradient inside the Block's data-gradient launch): CGEN_BLK3_DOWN=0 restores the separate launches.
+        # Served at the widths of that instance (in ukbb192: the 32 -> 8 -> 64 Block of the 192x192 stage; cgen_block3_supported decides); LABNOTES 25
+        self.blk3_down = int(os.environ.get("CGEN_BLK3_DOWN", "1")) if self.dt == F16 else 0
         # ... at which image sides: CGEN_BLK3_RES for Blocks with one or two input segments (trunk / prior / down Blocks),
         # CGEN_BLK3_RES3 for three-segment Blocks (the posterior: cat[h, pa, acts]); a comma list of sides and lo-hi ranges,
         # "0" = every side >= CGEN_BLK3_MINRES.  Defaults = where the fused launch beats the two it replaces INSIDE the step on MI355X
@@ -753,11 +757,16 @@ class Engine(WgradMixin):
             out.append((int(lo), int(hi or lo)))
         return out
 
-    def block2(self, site1, site2, segs, act, res1=None, trunk=False):
+    def block2(self, site1, site2, segs, act, res1=None, trunk=False, proj=None, down=0):
         """A whole light Block -- conv3x3(act(cat segs)) -> conv3x3(act(.)) (+ res1), vae.py:60-71,73-84 -- as ONE launch of
         cgen_block3 (csrc/block.hip) where the kernel serves the shape and the policy (blk3_res / blk3_res3) takes it, else as the
-        two conv launches.  The bottleneck tensor is written either way (weight gradients, backward mask)."""
+        two conv launches.  The bottleneck tensor is written either way (weight gradients, backward mask).
+        `proj`, `down`: a down Block (vae.py:70-84) -- the residual is the 1x1 conv `proj` of the raw input and the sum is average-
+        pooled by `down`: the POOLED tensor when that too goes into the launch, else None and nothing has been done (the caller
+        runs the projection, the Block and the pool as launches of their own)."""
         x0 = segs[0]
+        if proj is not None:
+            return self._block3_down_fwd(proj, site1, site2, segs, down)
         res_ok = self.blk3_res3 if len(segs) >= 3 else self.blk3_res
         small = self.blk3_small and x0.w <= 14 and x0.h <= 64 and min(x0.h, x0.w) >= 4  # (the small-image instance: csrc/block.hip blk3s)
         tile_ok = (min(x0.h, x0.w) >= self.blk3_minres and site1.co <= 32
@@ -808,6 +817,64 @@ class Engine(WgradMixin):
                 self.tape.append((self._bw_conv, (site2, [t], ACT_RELU, out, res1, None), self._bw_tag))
         return out
 
+    def _ghost(self, n, h, w, c):
+        """The handle of a tensor that is never materialised (no storage: a NULL view): it stands on the tape for its GRADIENT buffer."""
+        cp = _ceil(c, 8)
+        return NT(0, n, h, w, c, h * w * cp, w * cp, cp, self.es)
+
+    def _block3_down_fwd(self, proj, site1, site2, segs, down):
+        """The encoder's down Block as ONE launch of cgen_block3 (row-streaming instance): out = avg_pool2d(proj(x) + conv(x), 2); None
+        (and nothing done) when the knob is off or the kernel declines.  The projected residual and the un-pooled sum exist as handles
+        only; the tape gets today's three entries (projection conv, Block, pool), so backward() runs on it unchanged."""
+        x0 = segs[0]
+        if not (self.blk3_down and self.blk3_on and self.blk3_rows and len(segs) == 1 and isinstance(down, int) and down == 2
+                and proj.ks == 1 and proj.img_fwd is not None and "a_fwd" in site1.frag and "b_fwd" in site2.frag
+                and "a16_fwd" in site1.frag and x0.h % 2 == 0 and x0.w % 2 == 0):
+            return None
+        pc = proj.conv
+        assert (proj.ci == x0.c == site1.ci and proj.co == site2.co and tuple(pc.stride) == (1, 1) and tuple(pc.padding) == (0, 0)
+                and pc.groups == 1), (proj.name, "not a plain 1x1 projection of this Block's input onto its output width")
+        a = _lib.Block3Args()
+        a.dtype, a.n, a.h, a.w, a.nseg, a.nout, a.pre_act = self.dt, x0.n, x0.h, x0.w, 1, 1, 1
+        a.seg[0] = x0.cv()
+        b1, b2, bp = site1.conv.bias, site2.conv.bias, proj.conv.bias
+        a.w_a, a.bias_a = site1.frag["a_fwd"], (b1.data_ptr() if b1 is not None else None)
+        a.w_a16 = site1.frag["a16_fwd"]
+        a.w_proj, a.bias_proj, a.proj_krow, a.pool = proj.img_fwd, (bp.data_ptr() if bp is not None else None), proj.krow, 2
+        o = a.o[0]
+        o.w, o.bias = site2.frag["b_fwd"], (b2.data_ptr() if b2 is not None else None)
+        o.aux, o.res1 = NULL_VIEW, NULL_VIEW
+        # (asked first on DENSE views of the two tensors' shapes at the input's address, as `new` will lay them out: nothing is
+        #  allocated for a Block the kernel declines)
+        def dense(h, w, c):
+            cp = _ceil(c, 8)
+            return View(x0.ptr, h * w * cp, w * cp, cp, c, 0)
+
+        a.mid, o.out = dense(x0.h, x0.w, site1.co), dense(x0.h // 2, x0.w // 2, site2.co)
+        if self.lib.block3_supported(C.byref(a)) != 2:
+            return None
+        t = self.new(x0.n, x0.h, x0.w, site1.co)
+        pooled = self.new(x0.n, x0.h // 2, x0.w // 2, site2.co)
+        a.mid, o.out = t.cv(), pooled.cv()
+        if self.lib.block3_supported(C.byref(a)) != 2:  # (cannot differ: fresh arena tensors are aligned and dense)
+            raise RuntimeError("cgen_block3 declines the down Block's own tensors after serving the probe: %s" % (x0.shape,))
+        if not self._ablated(x0):
+            self._timed("conv_fwd", (proj, site1, site2), x0, lambda: self.lib.block3(C.byref(a), self.stream))
+        if self.recording:
+            res = self._ghost(x0.n, x0.h, x0.w, site2.co)
+            out = self._ghost(x0.n, x0.h, x0.w, site2.co)
+            if self._dbg_names is not None:
+                self._dbg_names[id(res.base)] = proj.name
+                self._dbg_names[id(out.base)] = site2.name
+            self.tape.append((self._bw_conv, (proj, segs, ACT_NONE, res, None, None), self._bw_tag))
+            if self.blk3_on >= 2:
+                self.tape.append((self._bw_block3, BlockRec((site1, site2), segs, (t,), out, res), self._bw_tag))
+            else:
+                self.tape.append((self._bw_conv, (site1, segs, ACT_RELU, t, None, None), self._bw_tag))
+                self.tape.append((self._bw_conv, (site2, [t], ACT_RELU, out, res, None), self._bw_tag))
+            self.tape.append((self._bw_pool, (out, pooled, down)))
+        return pooled
+
     def _ablated(self, x0, site=None, tag=None):
         """TIMING-ONLY ablation (CGEN_ABLATE, wrong results): is this launch skipped?  Resolution tokens (r24 ...) apply to every
         launch; with a `site` (single convs) also r12 and `tag`: "f1" the first conv of every Block, "d3" the data gradient of its
@@ -819,10 +886,30 @@ class Engine(WgradMixin):
             return True
         return any(x0.h == r and ("r%d" % r) in ab for r in (24, 48, 96, 192))
 
-    def _block3_dgrad_args(self, site1, site2, g, gmid, t, outs):
+    def _down_proj(self, segs, res1, blk_out, nbr):
+        """The projection site of a down Block whose backward this is, when its data gradient can go into the Block's launch: the tape
+        entry behind the Block's is the 1x1 conv (no activation, no residual) that made `res1` from the same single input, nothing
+        else has contributed to grad(res1), and the input wants that gradient.  Else None."""
+        prv, nxt = nbr if nbr is not None else (None, None)
+        if not (self.blk3_down and self.blk3_rows and nxt is not None and nxt[0] == self._bw_conv and res1 is not None and len(segs) == 1):
+            return None
+        # prv: the entry that ran before the Block's -- the 2x2 pool of its output: the shapes the forward form serves
+        if not (prv is not None and prv[0] == self._bw_pool and prv[1][0] is blk_out and isinstance(prv[1][2], int) and prv[1][2] == 2
+                and blk_out.h % 2 == 0 and blk_out.w % 2 == 0):
+            return None
+        site, psegs, act, out, r1, r2 = nxt[1]
+        ok = (site.ks == 1 and act == ACT_NONE and r1 is None and r2 is None and out is res1 and res1.base is res1 and res1.rg
+              and id(res1) not in self.grads and id(res1) not in self._riders and len(psegs) == 1 and psegs[0] is segs[0]
+              and segs[0].rg and site.seg_rg[0] and site.img_dg[0] is not None and not self._ablate)
+        return site if ok else None
+
+    def _block3_dgrad_args(self, site1, site2, g, gmid, t, outs, proj=None):
         """cgen_block3_args of a light Block's data gradient: grad(out) `g` -> grad(bottleneck) `gmid` (masked by the bottleneck `t`)
-        -> one output per (segment index, target view, forward tensor, view to add or None) of `outs`."""
+        -> one output per (segment index, target view, forward tensor, view to add or None) of `outs`.  `proj`: a down Block's
+        projection site, whose data gradient W_p^T g the launch adds to its output."""
         a = _lib.Block3Args()
+        if proj is not None:
+            a.w_proj, a.proj_krow = proj.img_dg[0], proj.krow_dg
         a.dtype, a.n, a.h, a.w, a.nseg, a.nout, a.pre_act = self.dt, g.n, g.h, g.w, 1, len(outs), 0
         a.seg[0] = g.cv()
         a.w_a, a.bias_a = site2.frag["a_dg"], None
@@ -834,7 +921,7 @@ class Engine(WgradMixin):
             a.o[j].res1 = prev.cv() if prev is not None else NULL_VIEW
         return a
 
-    def _bw_block3(self, sites, segs, mids, out, res1):
+    def _bw_block3(self, sites, segs, mids, out, res1, nbr=None):
         """Backward of a fused light Block: weight gradients as for the two convs (deferred, batched); the two data-gradient
         convs as ONE launch of cgen_block3 (pre_act = 0) -- with two outputs when two segments need a gradient (the posterior
         Block: h and the encoder activation) -- else the two conv launches."""
@@ -847,9 +934,14 @@ class Engine(WgradMixin):
         dsegs = [k for k, sg in enumerate(segs) if sg.rg and site1.seg_rg[k]]
         ok = (1 <= len(dsegs) <= 2 and "a_dg" in site2.frag and all(("b_dg", k) in site1.frag for k in dsegs)
               and all(segs[k].c % 8 == 0 for k in dsegs) and g.c % 8 == 0)
+        proj = self._down_proj(segs, res1, out, nbr) if ok and len(dsegs) == 1 else None
         if ok:  # (a probe on the forward tensors' views: the gradient views are not acquired yet)
-            probe = self._block3_dgrad_args(site1, site2, g, t, t, [(k, segs[k], segs[k], None) for k in dsegs])
+            probe = self._block3_dgrad_args(site1, site2, g, t, t, [(k, segs[k], segs[k], None) for k in dsegs], proj)
             ok = bool(self.lib.block3_supported(C.byref(probe)))
+            if not ok and proj is not None:  # the kernel declines the projection term: the Block as before, the projection's own entry
+                proj = None
+                probe = self._block3_dgrad_args(site1, site2, g, t, t, [(k, segs[k], segs[k], None) for k in dsegs])
+                ok = bool(self.lib.block3_supported(C.byref(probe)))
         if not ok:
             self._blk3.flush()
             self._bw_conv(site2, [t], act, out, res1, None)
@@ -864,7 +956,7 @@ class Engine(WgradMixin):
         gt, acc_t = self.grad_write(t)
         assert not acc_t
         tgt = [(k,) + self._dgrad_target(segs[k]) for k in dsegs]
-        a = self._block3_dgrad_args(site1, site2, g, gt, t, [(k, gv, segs[k], prev if acc else None) for (k, gv, prev, acc) in tgt])
+        a = self._block3_dgrad_args(site1, site2, g, gt, t, [(k, gv, segs[k], prev if acc else None) for (k, gv, prev, acc) in tgt], proj)
         x0 = segs[0]
         late = (lambda: self._wgrad(site1, segs, act, gt)) if (self._needs_wgrad(site1) and "wg" not in self._ablate) else (lambda: None)
         if self._ablated(x0):
@@ -873,6 +965,18 @@ class Engine(WgradMixin):
             # tensors this launch writes / reads (storage identity): a pair must not touch each other's
             wr = {id(gt.base)} | {id(gv.base) for (_, gv, _, _) in tgt}
             rd = {id(g.base), id(t.base)} | {id(segs[k].base) for (k, _, _, _) in tgt} | {id(prev.base) for (_, _, prev, acc) in tgt if acc}
+            if proj is not None:
+                # the projection's tape entry is absorbed: its data gradient went into this launch, its weight gradient is
+                # registered where its own entry would have (behind the Block's first conv's), on grad(res1)
+                g_res, late1 = self.grad_read(res1), late
+
+                def late():
+                    late1()
+                    if self._needs_wgrad(proj) and "wg" not in self._ablate:
+                        self._wgrad(proj, segs, ACT_NONE, g_res)
+
+                self._blk3.submit(a, wr, rd, (sites + (proj,), x0), late)
+                return 1  # (the projection's entry, behind this one)
             self._blk3.submit(a, wr, rd, (sites, x0), late)
             return
         else:
@@ -1532,7 +1636,12 @@ class Engine(WgradMixin):
                 other.flush()
                 if on and slot.held is None and may_pair(tape[i], tape[i - 1] if i > 0 else None):
                     slot.arm()
-                fn(*args)
+                if fn == self._bw_block3:
+                    # (its neighbours on the tape -- a down Block's pool in front, its projection conv behind: _down_proj; it answers
+                    #  how many of the entries behind it its launch has absorbed)
+                    skip += fn(*args, nbr=(tape[i + 1] if i + 1 < len(tape) else None, tape[i - 1] if i > 0 else None)) or 0
+                else:
+                    fn(*args)
                 slot.disarm()  # (if still armed: it did not reach its launch point)
             else:
                 self._blk3.flush()

@@ -126,6 +126,11 @@ def run_block(eng, blk, segs):
     act = ACT_RELU if blk.light else ACT_GELU
     cs = blk.convs()
     res = None
+    if blk.residual and blk.light and len(cs) == 2 and blk.d and segs[0].c != cs[-1].out_channels:
+        # a down Block (vae.py:70-84): projection, residual add and pooling inside the Block's launch where the kernel serves it
+        h = eng.block2(site(cs[0]), site(cs[1]), segs, act, trunk=True, proj=site(blk.width_proj), down=blk.d)
+        if h is not None:
+            return h
     if blk.residual:
         x = segs[0]
         if x.c != cs[-1].out_channels:

@@ -125,6 +125,22 @@ typedef struct cgen_block3_args {
   const void* w_a16; /* optional (NULL: absent): the first conv's weights as the 16-row image of cgen_weight_prep modes 6 / 7, which the
                       * row-streaming instance (wide images, one input segment of 32 or 64 channels, bottleneck <= 16: the 96x96 and
                       * 192x192 Blocks) reads; without it those shapes run on the tile instance */
+  /* The encoder's DOWN Block (vae.py:70-84: out = width_proj(x) + conv(x), then avg_pool2d(out, 2)) in the same launch.  Fields added at
+   * the end (additive in ABI 411: every caller zero-initialises the struct); NULL / 0 = the behaviour above.  Row-streaming instance only:
+   * with any of them set, cgen_block3_supported answers 0 for everything else (odd H or W, a float down-rate, remainder planes, other
+   * widths) and the caller runs the separate launches.
+   *   pre_act = 1: w_proj = the FORWARD image (cgen_weight_prep mode 0, row stride proj_krow elements) of a 1x1 conv over the RAW seg[0]
+   *                (no ReLU), bias_proj its bias; pool = 2 (required with w_proj).  o[0].res1 must be absent; o[0].out is the POOLED tensor
+   *                (n, h / 2, w / 2, Co):  out = avg2x2( rn16( conv3x3(relu(mid)) + bias + rn16(w_proj . seg[0] + bias_proj) ) ), the four
+   *                values summed in f32 in the order (0,0) (0,1) (1,0) (1,1) like cgen_avgpool_fwd.  Neither the projected residual nor the
+   *                un-pooled output is written.
+   *   pre_act = 0: w_proj = the DATA-GRADIENT image (mode 1) of that 1x1 conv, pool = 0:
+   *                o[0].out = rn16(conv3x3(mid) * relu'(o[0].aux) + o[0].res1) + w_proj^T . seg[0]   (seg[0] = grad_out at the centre pixel)
+   * The 1x1 sums are formed as cgen_conv2d's pixel kernel forms them (v_mfma_f32_16x16x32, 32 channels per step, bias first): on the
+   * image sizes that kernel serves (more than 6 000 pixels) the results have the bits of the three launches each way. */
+  const void* w_proj;
+  const float* bias_proj;
+  int32_t proj_krow, pool;
 } cgen_block3_args;
 int cgen_block3_supported(const cgen_block3_args* a);
 int cgen_block3(const cgen_block3_args* a, cgen_stream_t stream);
