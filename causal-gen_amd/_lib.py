@@ -93,6 +93,16 @@ class PredTrainHead(C.Structure):
                 ("ggamma", C.c_void_p * 7), ("gbeta", C.c_void_p * 7)]
 
 
+class MlpTrainHead(C.Structure):
+    """cgen_mlp_train_head: one scalar head (layers.py MLP) in training mode -- input columns with their row strides, the raw
+    weights, the two BatchNorms and every gradient."""
+    _fields_ = [("nin", C.c_int32), ("width", C.c_int32), ("tanh_loc", C.c_int32), ("obs_stride", C.c_int32), ("std_fixed", C.c_float),
+                ("reserved", C.c_int32), ("in_", C.c_void_p * 8), ("in_stride", C.c_int64 * 8), ("obs", C.c_void_p), ("w", C.c_void_p * 3),
+                ("bias", C.c_void_p), ("gamma", C.c_void_p * 2), ("beta", C.c_void_p * 2), ("running_mean", C.c_void_p * 2),
+                ("running_var", C.c_void_p * 2), ("num_batches_tracked", C.c_void_p * 2), ("gw", C.c_void_p * 3), ("gb", C.c_void_p),
+                ("ggamma", C.c_void_p * 2), ("gbeta", C.c_void_p * 2)]
+
+
 class AugmentArgs(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("c", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32), ("r_h", C.c_int32),
                 ("r_w", C.c_int32), ("pad_x", C.c_int32), ("pad_y", C.c_int32), ("ctx", C.c_int32), ("stream_id", C.c_uint32),
@@ -162,6 +172,7 @@ METRIC_MAX_VARS, METRIC_ACC = 8, 8
 STREAM_AUGMENT = 980  # Philox stream id of cgen_batch_augment (the list of taken ids is in csrc/common.h)
 PRED_NORMAL, PRED_CATEGORICAL, PRED_BERNOULLI = 0, 1, 2
 PRED_MAX_HEADS, PRED_MAX_OUT = 4, 16
+MLP_MAX_IN, MLP_MAX_WIDTH = 8, 64
 
 i32, i64, u32, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p
 
@@ -204,6 +215,7 @@ PROTOTYPES = {
     "cgen_nhwc_to_nchw": [i32, i32, i32, i32, i32, View, vp, vp],
     "cgen_batch_augment": [C.POINTER(AugmentArgs), vp],
     "cgen_batch_augment_arm": [C.POINTER(AugmentArgs)],
+    "cgen_batch_augment_planar": [C.POINTER(AugmentArgs), vp],
     "cgen_stem_conv_supported": [i32, i32, i32, i32],
     "cgen_stem_conv_fwd": [i32, i32, i32, i32, i32, i32, i32, View, vp, vp, View, vp],
     "cgen_im2col": [i32, i32, i32, i32, i32, View, View, vp],
@@ -257,6 +269,9 @@ PROTOTYPES = {
     "cgen_predictor_train_workspace": [C.POINTER(PredTrainHead), i32, i32, C.POINTER(i64)],
     "cgen_predictor_train_fwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, f32, vp, vp, vp, vp],
     "cgen_predictor_train_bwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, vp, vp, vp],
+    "cgen_mlp_train_workspace": [C.POINTER(MlpTrainHead), i32, C.POINTER(i64)],
+    "cgen_mlp_train_fwd": [C.POINTER(MlpTrainHead), i32, vp, i64, f32, vp, vp, vp],
+    "cgen_mlp_train_bwd": [C.POINTER(MlpTrainHead), i32, vp, i64, vp, vp],
     "cgen_pgm_workspace": [C.POINTER(PgmMech), i32, i32, C.POINTER(i64)],
     "cgen_pgm_nll_fwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp],
     "cgen_pgm_nll_fwd_bwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp, vp, i64, vp],

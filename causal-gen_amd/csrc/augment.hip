@@ -12,6 +12,8 @@
 //   PIX arm  (the engine's own tensors: pixel stride rounded up to 8 channels, or a channel slice of a wider tensor): a lane owns one
 //            pixel and writes its max(c, cpad) channels -- the zero padding included -- as whole 16-byte groups when the view is
 //            aligned, element by element otherwise.
+// cgen_batch_augment_planar is one more instance of the kernel for the consumers that read contiguous f32 NCHW (the anticausal
+// predictors): a lane owns one element of [c, r_h, r_w], 4-byte stores, same draws and same per-pixel arithmetic.
 #include "common.h"
 
 namespace cgen {
@@ -30,7 +32,7 @@ struct AugP {
   float* pa_out;
 };
 
-enum { AUG_ROW = 0, AUG_PIX_VEC = 1, AUG_PIX_SCALAR = 2 };
+enum { AUG_ROW = 0, AUG_PIX_VEC = 1, AUG_PIX_SCALAR = 2, AUG_PLANAR = 3 };
 
 template <typename T> union AugPack { T e[16 / sizeof(T)]; uint4 v; };
 
@@ -101,6 +103,14 @@ __global__ __launch_bounds__(256) void batch_augment_kernel(AugP a, View out, in
         const int x = e0 / a.c, ch = e0 - x * a.c;
         Elem<T>::st(dst + e0, aug_px(a, d, ch, y, x));
       }
+    }
+  } else if (MODE == AUG_PLANAR) {
+    // contiguous [n, c, r_h, r_w]: a lane owns one element, consecutive lanes consecutive pixels of a plane
+    const int hw = a.rh * a.rw, items = a.c * hw;
+    T* dst = (T*)out.p + (int64_t)b * items;
+    for (int i = chunk * 256 + threadIdx.x; i < items; i += chunks * 256) {
+      const int ch = i / hw, q = i - ch * hw, y = q / a.rw, x = q - y * a.rw;
+      Elem<T>::st(dst + i, aug_px(a, d, ch, y, x));
     }
   } else {
     const int items = a.rh * a.rw;
@@ -185,15 +195,19 @@ extern "C" int cgen_batch_augment_arm(const cgen_augment_args* a) {
   return rc != CGEN_OK ? rc : pl.arm;
 }
 
+static void aug_params(AugP& p, const cgen_augment_args* a) {
+  p.n = a->n; p.c = a->c; p.h0 = a->h0; p.w0 = a->w0; p.rh = a->r_h; p.rw = a->r_w; p.padx = a->pad_x; p.pady = a->pad_y;
+  p.ctx = a->ctx; p.stream_id = a->stream_id; p.p = a->hflip_p; p.sub = a->sub; p.mul = a->mul; p.n_data = a->n_data;
+  p.data = (const uint8_t*)a->data; p.index = a->index; p.rng = a->rng; p.draws_in = a->draws_in; p.draws_out = a->draws_out;
+  p.pa_data = a->pa_data; p.pa_out = a->pa_out;
+}
+
 extern "C" int cgen_batch_augment(const cgen_augment_args* a, cgen_stream_t stream) {
   AugPlan pl;
   const int rc = aug_plan(a, &pl);
   if (rc != CGEN_OK) return rc;
   AugP p;
-  p.n = a->n; p.c = a->c; p.h0 = a->h0; p.w0 = a->w0; p.rh = a->r_h; p.rw = a->r_w; p.padx = a->pad_x; p.pady = a->pad_y;
-  p.ctx = a->ctx; p.stream_id = a->stream_id; p.p = a->hflip_p; p.sub = a->sub; p.mul = a->mul; p.n_data = a->n_data;
-  p.data = (const uint8_t*)a->data; p.index = a->index; p.rng = a->rng; p.draws_in = a->draws_in; p.draws_out = a->draws_out;
-  p.pa_data = a->pa_data; p.pa_out = a->pa_out;
+  aug_params(p, a);
   const dim3 g((unsigned)(a->n * pl.chunks)), blk(256);
   hipStream_t st = (hipStream_t)stream;
 #define AUG_LAUNCH(T_, M_) hipLaunchKernelGGL((batch_augment_kernel<T_, M_>), g, blk, 0, st, p, mk(a->out), pl.chunks, pl.groups, pl.tail, pl.cw)
@@ -204,4 +218,28 @@ extern "C" int cgen_batch_augment(const cgen_augment_args* a, cgen_stream_t stre
   }
 #undef AUG_LAUNCH
   return check_launch("cgen_batch_augment");
+}
+
+extern "C" int cgen_batch_augment_planar(const cgen_augment_args* a, cgen_stream_t stream) {
+  const char* fn = "cgen_batch_augment_planar";
+  CGEN_REQUIRE(a, "%s: null args", fn);
+  CGEN_REQUIRE(a->dtype == CGEN_F32, "%s: the planar output is f32 (dtype %d)", fn, a->dtype);
+  CGEN_REQUIRE(a->c >= 1 && a->c <= 4, "%s: c must be 1..4 (got %d)", fn, a->c);
+  // everything that is not about the output view is cgen_batch_augment's own check, made on the NHWC view of the same memory
+  cgen_augment_args q = *a;
+  q.out.sn = (int64_t)a->c * a->r_h * a->r_w; q.out.sh = (int64_t)a->c * a->r_w; q.out.sw = a->c; q.out.cpad = 0;
+  AugPlan pl;
+  const int rc = aug_plan(&q, &pl);
+  if (rc != CGEN_OK) return rc;
+  CGEN_REQUIRE(a->out.sn == (int64_t)a->c * a->r_h * a->r_w && a->out.sh == a->r_w && a->out.sw == 1 && a->out.cpad <= a->c,
+               "%s: out must be a contiguous [n, c, r_h, r_w] (sn %lld, sh %lld, sw %lld, cpad %d)", fn, (long long)a->out.sn,
+               (long long)a->out.sh, (long long)a->out.sw, a->out.cpad);
+  int64_t chunks = ((int64_t)a->c * a->r_h * a->r_w + 255) / 256;
+  if (chunks > 256) chunks = 256;
+  CGEN_REQUIRE((int64_t)a->n * chunks < (1ll << 31), "%s: batch too large", fn);
+  AugP p;
+  aug_params(p, a);
+  hipLaunchKernelGGL((batch_augment_kernel<float, AUG_PLANAR>), dim3((unsigned)(a->n * chunks)), dim3(256), 0, (hipStream_t)stream, p,
+                     mk(a->out), (int)chunks, 0, 0, a->c);
+  return check_launch(fn);
 }

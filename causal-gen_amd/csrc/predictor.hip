@@ -6,6 +6,8 @@
 // latency-bound.  Tiled (second half of this file): one launch per layer over (tile x channel group x image x head), for the
 // large images whose 32 workgroups would leave the chip idle.  Training mode (batch-statistic BatchNorm, parameter gradients) is
 // predictor_train.inc, included at the end of this file: it shares the geometry, the likelihoods and the tiled data gradients.
+// The scalar head that sees no image (pgm/layers.py MLP, encoder_a) is trained by predictor_mlp.inc, included after it: it
+// shares the Normal likelihood.
 //
 // Backward recomputes the head's forward, then walks back IN PLACE: the gradient of a layer's output overwrites that layer's
 // post-activation once its LeakyReLU mask has been read (LeakyReLU keeps the sign, so the post-activation is the mask).  The
@@ -1016,3 +1018,4 @@ extern "C" int cgen_predictor_tiled_bwd(const cgen_pred_head* heads, int32_t nhe
 }
 
 #include "predictor_train.inc"
+#include "predictor_mlp.inc"

@@ -101,9 +101,16 @@ class DeviceDataset:
             self.rng = torch.tensor([torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, 0], dtype=torch.int64, device=self.device)
         return self.rng
 
-    def batch(self, index, train=True, draws=None, return_draws=False, dtype=None, rng=None):
+    def planar_view(self, ptr, train=True):
+        """The ``cgen_view`` that tells ``cgen_batch_augment_planar`` its output is a contiguous f32 [n, c, r_h, r_w] at `ptr`."""
+        r_h, r_w, _, _, _ = self.geometry(train)
+        return _lib.View(ptr, self.c * r_h * r_w, r_w, 1, self.c, 0)
+
+    def batch(self, index, train=True, draws=None, return_draws=False, dtype=None, rng=None, planar=False):
         """{"x", "pa"} for the rows `index` (device int64 vector): ``x`` has NCHW shape over NHWC memory (the f32 engine takes it
         zero-copy, engine.from_nchw's channels-last branch), in `dtype` (f32, or the library's 16-bit storage format).
+        `planar`: ``x`` is a contiguous f32 NCHW tensor instead (``cgen_batch_augment_planar``: what the anticausal predictors
+        read), the same values bit for bit.
         `draws` (int32 [n, 3] of (oy, ox, flip)) overrides the random draws; `return_draws` adds the ones used as "draws".
         `rng`: a device int64 {seed, offset} tensor to draw from as it stands; by default the data set's own state, moved on by
         one per training batch (the launch itself never advances a state)."""
@@ -114,9 +121,11 @@ class DeviceDataset:
         h16 = torch.bfloat16 if lib.h16_is_bf16 else torch.float16
         if dtype not in (torch.float32, h16):
             raise ValueError(f"dtype must be torch.float32 or {h16} (the library's 16-bit format), got {dtype}")
+        if planar and dtype != torch.float32:
+            raise ValueError(f"the planar batch is f32 (got {dtype})")
         r_h, r_w, _, _, _ = self.geometry(train)
         st = torch.cuda.current_stream(self.device).cuda_stream
-        out = torch.empty((n, r_h, r_w, self.c), dtype=dtype, device=self.device)
+        out = torch.empty((n, self.c, r_h, r_w) if planar else (n, r_h, r_w, self.c), dtype=dtype, device=self.device)
         pa = torch.empty((n, self.ctx), dtype=torch.float32, device=self.device)
         d_in = None
         if draws is not None:
@@ -127,12 +136,12 @@ class DeviceDataset:
             if train:
                 lib.rng_advance(rng.data_ptr(), 1, st)
         d_out = torch.empty((n, 3), dtype=torch.int32, device=self.device) if return_draws else None
-        view = _lib.View(out.data_ptr(), r_h * r_w * self.c, r_w * self.c, self.c, self.c, 0)
+        view = self.planar_view(out.data_ptr(), train) if planar else _lib.View(out.data_ptr(), r_h * r_w * self.c, r_w * self.c, self.c, self.c, 0)
         a = self.args_for(_lib.F32 if dtype == torch.float32 else _lib.F16, n, index.data_ptr(), view,
                           None if rng is None else rng.data_ptr(), train, None if d_in is None else d_in.data_ptr(),
                           None if d_out is None else d_out.data_ptr(), pa.data_ptr())
-        lib.batch_augment(C.byref(a), st)
-        res = {"x": out.permute(0, 3, 1, 2), "pa": pa}
+        (lib.batch_augment_planar if planar else lib.batch_augment)(C.byref(a), st)
+        res = {"x": out if planar else out.permute(0, 3, 1, 2), "pa": pa}
         if return_draws:
             res["draws"] = d_out
         return res

@@ -11,7 +11,8 @@ nothing here has a training mode.)
 
 ``model_anticausal(**obs)`` returns the summed negative log-likelihood (what pyro's ``Trace_ELBO.differentiable_loss`` of the
 anticausal model with the empty guide computes); ``AnticausalELBO`` hands it to ``DSCM.forward`` as ``elbo_fn``.
-``encoder_a`` (UKBB age from two scalars) does not see the image and stays host-side torch, as the parent SCMs do (pgm.py).
+``encoder_a`` (UKBB age from two scalars) does not see the image: its eval forward stays host-side torch, as the parent SCMs' does
+(pgm.py); ``PredictorTrainStep(scalar_heads=True)`` trains it on the device (csrc/predictor_mlp.inc).
 """
 import ctypes
 import os
@@ -101,7 +102,8 @@ class CNN(nn.Module):
 
 
 class MLP(nn.Module):
-    """layers.py:46-59 (``encoder_a``): host-side torch in eval mode -- two scalars in, no image."""
+    """layers.py:46-59 (``encoder_a``): host-side torch in eval mode -- two scalars in, no image.  (Its training mode is
+    ``cgen_mlp_train_*``, run by ``PredictorTrainStep(scalar_heads=True)`` on these very parameters.)"""
 
     def __init__(self, num_inputs=1, width=32, num_outputs=1):
         super().__init__()
@@ -115,6 +117,14 @@ class MLP(nn.Module):
 
     def forward(self, x):
         return self.mlp(x)
+
+
+class _ScalarHead:
+    """One scalar head of a PGM: its MLP, the variable it scores as Normal(loc, f(logscale)) and the observed variables it reads,
+    in the order they are concatenated."""
+
+    def __init__(self, mlp, var, inputs, tanh_loc=False):
+        self.mlp, self.var, self.inputs, self.tanh_loc = mlp, var, tuple(inputs), tanh_loc
 
 
 class _Head:
@@ -289,6 +299,10 @@ class _AnticausalPredictor(nn.Module):
     def _heads(self):
         raise NotImplementedError
 
+    def _scalar_heads(self):
+        """The heads that see no image (``predictor_train.PredictorTrainStep(scalar_heads=True)`` trains them): none by default."""
+        return []
+
     def train(self, mode: bool = True):
         return super().train(False)
 
@@ -416,6 +430,9 @@ class FlowPredictor(_AnticausalPredictor):
                 _Head(self.encoder_b, _lib.PRED_NORMAL, False, "brain_volume", "ventricle_volume"),
                 _Head(self.encoder_s, _lib.PRED_BERNOULLI, False, "sex", "brain_volume"),
                 _Head(self.encoder_m, _lib.PRED_BERNOULLI, False, "mri_seq", None)]
+
+    def _scalar_heads(self):
+        return [_ScalarHead(self.encoder_a, "age", ("brain_volume", "ventricle_volume"))]  # (the order _age concatenates them in)
 
     def _age(self, obs):
         dev = self.encoder_a.mlp[0].weight.device

@@ -392,6 +392,12 @@ int cgen_batch_augment(const cgen_augment_args* a, cgen_stream_t stream);
  * 0 = contiguous rows, all 16-byte stores; 1 = contiguous rows, 16-byte stores + element-wise row end; 2 = contiguous rows, element-wise
  * (unaligned view); 3 = one pixel per lane, 16-byte stores (padded pixel stride); 4 = one pixel per lane, element-wise. */
 int cgen_batch_augment_arm(const cgen_augment_args* a);
+/* The same batch in PLANAR layout (additive in ABI 411): out.p is a contiguous f32 [n, c, r_h, r_w], what the anticausal predictors
+ * read (the second transforms.ToTensor-shaped copy the reference's sup_epoch feeds them).  Same arguments, same draws from the same
+ * Philox state and the same per-pixel arithmetic as cgen_batch_augment, so the two outputs hold the same values bit for bit.
+ * dtype must be CGEN_F32 and the view must say what the memory is: out.c = c, out.sn = c * r_h * r_w, out.sh = r_w, out.sw = 1,
+ * no channel padding.  (For c == 1 the NHWC launch writes this very memory.) */
+int cgen_batch_augment_planar(const cgen_augment_args* a, cgen_stream_t stream);
 
 /* ------------------------------------------------------------------ latent layer (K10, K16)
  * Fused sample_gaussian + gaussian_kl (vae.py:14-30, 268-269):
@@ -680,6 +686,54 @@ int cgen_predictor_train_fwd(const cgen_pred_train_head* heads, int32_t nheads, 
 /* dx (optional, NCHW like x) = coef_dev[0] * d(sum of terms)/dx; same heads, n, x and ws as the forward just run */
 int cgen_predictor_train_bwd(const cgen_pred_train_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, int64_t ws_floats,
                              const float* coef_dev, float* dx, cgen_stream_t);
+
+/* ------------------------------------------------------------------ scalar predictor head, TRAINING mode (additive in ABI 411; csrc/predictor_mlp.inc)
+ * pgm/layers.py MLP in train mode (layers.py:46-59), scored as flow_pgm.py:260-267 scores encoder_a: q(a | b, v) = Normal(MLP(b, v)).
+ *   mlp.0 Linear nin -> w (no bias), mlp.1 BatchNorm1d(w), LeakyReLU(0.01), mlp.3 Linear w -> w (no bias), mlp.4 BatchNorm1d(w),
+ *   LeakyReLU(0.01), mlp.6 Linear w -> 2 (bias); term[b] = -log Normal(obs[b]; loc, scale) with loc = out[0] (tanh(out[0]) with
+ *   tanh_loc) and scale = std_fixed > 0 ? std_fixed : softplus(out[1]): cgen_pred_head's NORMAL kind, the same device function.
+ * Both BatchNorms take the mean over the n rows first and then the BIASED variance about that mean in a second pass, and update
+ * running_mean / running_var as nn.BatchNorm1d does (momentum, unbiased variance n / (n - 1), num_batches_tracked += 1).
+ * Input column k of row b is in[k][b * in_stride[k]]: columns of separate buffers or of one wider row-major table are read in
+ * place, in the order torch.cat would put them.  There is no gradient to the inputs (observed parents).
+ * Served: 2 <= n <= 4096, 1 <= nin <= CGEN_MLP_MAX_IN, w a multiple of 8 up to CGEN_MLP_MAX_WIDTH, two outputs.
+ * LAUNCHES: ONE per direction, whatever n: a single workgroup of 1024 threads owns the whole batch, so every reduction over the
+ * batch runs inside it in a fixed order (per-thread sums over rows b = g, g + G, ..., merged in g order).  No atomics; reruns are
+ * bit-identical.  Capturable: one stream, no allocation, no synchronisation, no host read of device data.
+ * Workspace (floats): 3 * n * w (the two normalised pre-activations and one gradient plane) + 2 * n (the outputs) + 2 * w (1 / std). */
+#define CGEN_MLP_MAX_IN 8
+#define CGEN_MLP_MAX_WIDTH 64
+typedef struct cgen_mlp_train_head {
+  int32_t nin, width;               /* num_inputs, hidden width */
+  int32_t tanh_loc;                 /* loc = tanh(out[0]) */
+  int32_t obs_stride;               /* row stride (floats) of obs */
+  float std_fixed;                  /* > 0 = constant scale, else softplus(out[1]) */
+  int32_t reserved;
+  const float* in[CGEN_MLP_MAX_IN]; /* input columns, in[k][b * in_stride[k]] */
+  int64_t in_stride[CGEN_MLP_MAX_IN];
+  const float* obs;                 /* observed value, obs[b * obs_stride] */
+  const float* w[3];                /* mlp.0 [w][nin], mlp.3 [w][w], mlp.6 [2][w] */
+  const float* bias;                /* mlp.6 [2] */
+  const float* gamma[2];            /* mlp.1, mlp.4 weight */
+  const float* beta[2];             /* mlp.1, mlp.4 bias */
+  float* running_mean[2];
+  float* running_var[2];
+  int64_t* num_batches_tracked[2];
+  float* gw[3];                     /* gradients of w[0..2] */
+  float* gb;                        /* gradient of bias */
+  float* ggamma[2];
+  float* gbeta[2];
+} cgen_mlp_train_head;
+/* floats of workspace for n rows: 3 * n * width + 2 * n + 2 * width */
+int cgen_mlp_train_workspace(const cgen_mlp_train_head* rec, int32_t n, int64_t* floats);
+/* Forward: terms[b] (required, f32[n]) = the row's term; loss (optional, f32[1]): the sum of the terms, taken in a fixed order, is
+ * ADDED to the value already there (a step adds this head to the image heads' sum without a launch of its own; a caller that wants
+ * the head's sum alone zeroes it first).  momentum = BatchNorm's (0.1).  Leaves in ws what the backward reads. */
+int cgen_mlp_train_fwd(const cgen_mlp_train_head* rec, int32_t n, float* ws, int64_t ws_floats, float momentum, float* terms, float* loss,
+                       cgen_stream_t);
+/* Backward of the forward just run on the same rec, n and ws (it does not recompute it: the running statistics move once per
+ * step): every gradient of rec is OVERWRITTEN with coef_dev[0] * d(sum of terms)/d(parameter). */
+int cgen_mlp_train_bwd(const cgen_mlp_train_head* rec, int32_t n, float* ws, int64_t ws_floats, const float* coef_dev, cgen_stream_t);
 
 /* ------------------------------------------------------------------ counterfactual evaluation (additive in ABI 411: new symbols only, no struct, enum value or signature moved)
  * The numbers of the reference's evaluation half, accumulated on the device: train_cf.py:63-108 get_metrics over the predictions
