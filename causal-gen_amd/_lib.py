@@ -120,6 +120,15 @@ class LatentTailArgs(C.Structure):
                 ("coef", C.c_void_p), ("chan_scale", C.c_void_p)]
 
 
+class DgaussHeadArgs(C.Structure):
+    """cgen_dgauss_head_args: the two 1x1 likelihood heads fused with the discretised-Gaussian NLL, one launch each way."""
+    _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("hin", View),
+                ("img_loc", C.c_void_p), ("img_ls", C.c_void_p), ("bias_loc", C.c_void_p), ("bias_ls", C.c_void_p),
+                ("params", View), ("x", View), ("nll_part", C.c_void_p),
+                ("coef_dev", C.c_void_p), ("coef_stride", C.c_int32), ("nsplit", C.c_int32), ("g_h", View), ("g_params", View),
+                ("partial_w_loc", C.c_void_p), ("partial_b_loc", C.c_void_p), ("partial_w_ls", C.c_void_p), ("partial_b_ls", C.c_void_p)]
+
+
 class LatentTailFwdArgs(C.Structure):
     """cgen_latent_tail_fwd_args: a decoder layer's forward latent tail (reparam + KL, z_proj, z_feat_proj) as one launch."""
     _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("z_dim", C.c_int32), ("c", C.c_int32),
@@ -241,6 +250,9 @@ PROTOTYPES = {
     "cgen_like_chunks": [i32, i32],
     "cgen_dgauss_nll_fwd": [i32, i32, i32, i32, i32, View, View, vp, vp],
     "cgen_dgauss_nll_bwd": [i32, i32, i32, i32, i32, View, View, vp, i32, View, vp],
+    "cgen_dgauss_head_supported": [C.POINTER(DgaussHeadArgs)],
+    "cgen_dgauss_head_fwd": [C.POINTER(DgaussHeadArgs), vp],
+    "cgen_dgauss_head_bwd": [C.POINTER(DgaussHeadArgs), vp],
     "cgen_dgauss_params": [i32, i32, i32, i32, i32, View, View, f32, vp, vp, vp],
     "cgen_dgauss_sample": [i32, i32, i32, i32, i32, View, f32, vp, u32, vp, vp, vp],
     "cgen_gauss_nll_fwd": [i32, i32, i32, i32, i32, View, View, View, vp, u32, vp, vp],
@@ -286,7 +298,8 @@ _RESTYPES = {"cgen_last_error": C.c_char_p}
 ABI_VERSION = 411  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
 _NOCHECK = {"cgen_version", "cgen_h16_format", "cgen_last_error", "cgen_conv2d_wgrad_plan", "cgen_reparam_kl_chunks", "cgen_like_chunks",
             "cgen_block3_supported", "cgen_block4_supported", "cgen_block4_pair_supported", "cgen_block3_pair_supported", "cgen_conv2d_pair_supported", "cgen_stem_conv_supported",
-            "cgen_predictor_supported", "cgen_predictor_tiled_supported", "cgen_batch_augment_arm", "cgen_latent_tail_bwd_supported", "cgen_latent_tail_fwd_supported"}
+            "cgen_predictor_supported", "cgen_predictor_tiled_supported", "cgen_batch_augment_arm", "cgen_latent_tail_bwd_supported", "cgen_latent_tail_fwd_supported",
+            "cgen_dgauss_head_supported"}
 
 
 class WgradBatchLaunch(C.Structure):

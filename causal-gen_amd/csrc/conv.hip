@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "conv_shared.h"
+#include "like_head.h"
 
 namespace cgen {
 
@@ -1740,6 +1741,18 @@ static int conv_fill(const cgen_conv_args* a, ConvP& p) {
   p.epi_vec = epi_ok(a->out) && epi_ok(a->aux) && epi_ok(a->res1) && epi_ok(a->res2) && (!a->bias || ((uintptr_t)a->bias % 16 == 0));
   p.epi_vec16 = vec16_ok(a->out, esz) && vec16_ok(a->aux, esz) && vec16_ok(a->res1, esz) && vec16_ok(a->res2, esz) && (!a->bias || ((uintptr_t)a->bias % 16 == 0));
   return CGEN_OK;
+}
+
+// launch_conv's decision for one class of calls, without launching (like_head.h): not the small-image kernel, not conv_px /
+// conv_ws (both refuse an output they cannot write in 16-byte chunks of whole channel groups), hence conv_tile_kernel -- and
+// its K loop is a single step.
+bool cgen::conv_is_tile_1x1_onestep(const cgen_conv_args* a) {
+  ConvP p;
+  if (!a || a->dtype != CGEN_F16 || conv_fill(a, p) != CGEN_OK) return false;
+  if (p.KS != 1 || p.H < 5 || p.W < 5 || !p.dma_ok || p.force_generic || p.out_rem || p.r1_rem) return false;
+  if (smallp_takes(p)) return false;
+  if (p.Co % 4 == 0) return false;  // (conv_px or conv_ws may take it)
+  return p.ctot8 <= 32;
 }
 
 extern "C" int cgen_conv2d(const cgen_conv_args* a, cgen_stream_t stream) {

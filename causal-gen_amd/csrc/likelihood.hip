@@ -2,6 +2,7 @@
 // decode and their backward passes), ELBO assembly (vae.py:450-457) and the counterfactual pixel step (dscm.py:55-63) with
 // its backward over either head.  All f32 math; HBM-bound.
 #include "common.h"
+#include "like_head.h"
 
 namespace cgen {
 
@@ -16,6 +17,35 @@ __device__ __forceinline__ float dg_cdf(float u) { return 0.5f * (1.0f + tanhf(D
 __device__ __forceinline__ float dg_cdf_grad(float u) {
   const float t = tanhf(DG_K0 * (u + DG_K1 * u * u * u));
   return 0.5f * (1.f - t * t) * DG_K0 * (1.f + 3.f * DG_K1 * u * u);
+}
+
+// One channel of one pixel, shared by the stand-alone kernels and the fused head kernels (dgauss_head_*): log p of the
+// discretised Gaussian (vae.py:393-411; the edge bins at -1 / +1, the -9 clamp of the log-scale) ...
+__device__ __forceinline__ float dg_logp(float loc, float ls_raw, float xv) {
+  const float ls = fmaxf(ls_raw, DG_MIN_LS);
+  const float inv = expf(-ls), d = xv - loc;
+  const float cp = dg_cdf(inv * (d + 1.f / 255.f)), cm = dg_cdf(inv * (d - 1.f / 255.f));
+  float lp;
+  if (xv < -0.999f) lp = logf(fmaxf(cp, 1e-12f));
+  else if (xv > 0.999f) lp = logf(fmaxf(1.f - cm, 1e-12f));
+  else lp = logf(fmaxf(cp - cm, 1e-12f));
+  return lp;
+}
+// ... and coef * d(-log p) / d(loc, raw log-scale)
+__device__ __forceinline__ void dg_logp_grad(float loc, float ls_raw, float xv, float coef, float& gloc, float& gls) {
+  const float ls = fmaxf(ls_raw, DG_MIN_LS);
+  const float inv = expf(-ls), d = xv - loc;
+  const float up = inv * (d + 1.f / 255.f), um = inv * (d - 1.f / 255.f);
+  const float cp = dg_cdf(up), cm = dg_cdf(um);
+  float dup = 0.f, dum = 0.f;  // d lp / d up, d lp / d um
+  if (xv < -0.999f) { if (cp >= 1e-12f) dup = dg_cdf_grad(up) / cp; }
+  else if (xv > 0.999f) { if (1.f - cm >= 1e-12f) dum = -dg_cdf_grad(um) / (1.f - cm); }
+  else { const float de = cp - cm; if (de >= 1e-12f) { dup = dg_cdf_grad(up) / de; dum = -dg_cdf_grad(um) / de; } }
+  // up = inv*(d+1/255): d up/d loc = -inv ; d up/d ls = -up
+  const float dlp_dloc = -(dup + dum) * inv;
+  const float dlp_dls = (ls_raw >= DG_MIN_LS) ? -(dup * up + dum * um) : 0.f;
+  gloc = -coef * dlp_dloc;
+  gls = -coef * dlp_dls;
 }
 
 struct DgP {
@@ -60,16 +90,7 @@ __global__ __launch_bounds__(256) void dgauss_nll_fwd_kernel(DgP p) {
         loc[2] = loc[2] + k[1] * xv[0] + k[2] * xv[1];
         loc[1] = loc[1] + k[0] * xv[0];
       }
-      for (int c = 0; c < p.c; ++c) {
-        const float ls = fmaxf(lsr[c], DG_MIN_LS);
-        const float inv = expf(-ls), d = xv[c] - loc[c];
-        const float cp = dg_cdf(inv * (d + 1.f / 255.f)), cm = dg_cdf(inv * (d - 1.f / 255.f));
-        float lp;
-        if (xv[c] < -0.999f) lp = logf(fmaxf(cp, 1e-12f));
-        else if (xv[c] > 0.999f) lp = logf(fmaxf(1.f - cm, 1e-12f));
-        else lp = logf(fmaxf(cp - cm, 1e-12f));
-        acc -= lp;
-      }
+      for (int c = 0; c < p.c; ++c) acc -= dg_logp(loc[c], lsr[c], xv[c]);
     }
   }
   const float tot = block_sum_256(acc, sm);
@@ -91,21 +112,7 @@ __global__ __launch_bounds__(256) void dgauss_nll_bwd_kernel(DgP p) {
     }
     const float coef = p.coef[(int64_t)b * p.coef_stride];
     float gloc[3], gls[3];
-    for (int c = 0; c < p.c; ++c) {
-      const float ls = fmaxf(lsr[c], DG_MIN_LS);
-      const float inv = expf(-ls), d = xv[c] - loc[c];
-      const float up = inv * (d + 1.f / 255.f), um = inv * (d - 1.f / 255.f);
-      const float cp = dg_cdf(up), cm = dg_cdf(um);
-      float dup = 0.f, dum = 0.f;  // d lp / d up, d lp / d um
-      if (xv[c] < -0.999f) { if (cp >= 1e-12f) dup = dg_cdf_grad(up) / cp; }
-      else if (xv[c] > 0.999f) { if (1.f - cm >= 1e-12f) dum = -dg_cdf_grad(um) / (1.f - cm); }
-      else { const float de = cp - cm; if (de >= 1e-12f) { dup = dg_cdf_grad(up) / de; dum = -dg_cdf_grad(um) / de; } }
-      // up = inv*(d+1/255): d up/d loc = -inv ; d up/d ls = -up
-      const float dlp_dloc = -(dup + dum) * inv;
-      const float dlp_dls = (lsr[c] >= DG_MIN_LS) ? -(dup * up + dum * um) : 0.f;
-      gloc[c] = -coef * dlp_dloc;
-      gls[c] = -coef * dlp_dls;
-    }
+    for (int c = 0; c < p.c; ++c) dg_logp_grad(loc[c], lsr[c], xv[c], coef, gloc[c], gls[c]);
     T* go = vptr<T>(p.g, b, y, x);
     for (int c = 0; c < p.c; ++c) {
       Elem<T>::st(go + c, gloc[c]);
@@ -116,6 +123,194 @@ __global__ __launch_bounds__(256) void dgauss_nll_bwd_kernel(DgP p) {
       Elem<T>::st(go + 7, gloc[2] * xv[0] * (1.f - k[1] * k[1]));
       Elem<T>::st(go + 8, gloc[2] * xv[1] * (1.f - k[2] * k[2]));
     }
+  }
+}
+
+// ----------------------------------------------------------------------------- fused likelihood head (C = 1, f16)
+// The two 1x1 heads x_loc / x_logscale (vae.py:325-333) and the NLL around them, one launch each way, with the bits of the
+// launches they replace:
+//   forward   cgen_conv2d x 2 (conv_tile_kernel<h16, 1, 1>: the output is a channel of the 2-channel parameter tensor, which
+//             the 16-byte epilogues of conv_px / conv_ws cannot write) + dgauss_nll_fwd_kernel;
+//   backward  dgauss_nll_bwd_kernel + the two data gradients (conv_kernel<h16, 2>: grad_out is a one-channel slice, not
+//             DMA-clean) + the two weight gradients (wgrad_kernel<h16, 1>, same reason).
+struct DhP {
+  int n, h, w, ci, P, nsplit, pps, coef_stride;
+  Div32 d_hw, d_w;
+  View hin, params, x, gh, gparams;
+  const h16_t *w_loc, *w_ls;  // row 0 of the two sites' forward images: the Ci weights of the single output channel
+  const float *b_loc, *b_ls;
+  float* part;
+  const float* coef;
+  float *pw_loc, *pb_loc, *pw_ls, *pb_ls;
+};
+
+// Forward.  One block per (1024-pixel chunk, sample), dgauss_nll_fwd_kernel's grid.  Wave w forms the head sums of pixels
+// w * 256 .. + 256 of the chunk, 16 at a time, as conv_tile_kernel does: ONE v_mfma_f32_16x16x32 from zero accumulators, lane
+// group fg holding channels 8 fg .. + 8 of pixel (lane & 15); the bias is added in f32 and the sum rounded once.  Both heads are
+// rows of that MFMA (row 0: loc, row 1: logscale; the rows of an MFMA do not mix).  With 16 input channels conv_tile_kernel's
+// lane groups 2 and 3 re-read channels 0..15 against the zero columns 16..31 of the weight image; so does this kernel.
+// The rounded pairs cross to dgauss_nll_fwd_kernel's thread -> pixel mapping (chunk * 1024 + i * 256 + tid) through LDS, where
+// they are stored to the parameter tensor (4 bytes per pixel) and enter the same dg_logp / block_sum_256 chain.
+__global__ __launch_bounds__(256) void dgauss_head_fwd_kernel(DhP p) {
+  __shared__ float sm[4];
+  __shared__ uint32_t ps[LIKE_PIX];
+  const int b = blockIdx.y, chunk = blockIdx.x;
+  const int npix = p.h * p.w;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
+  h16x8 aw;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) aw[e] = (h16n_t)0.f;
+  if (fr < 2 && fg * 8 < p.ci) aw = *(const h16x8*)((fr == 0 ? p.w_loc : p.w_ls) + fg * 8);
+  const int coff = (fg * 8) & (p.ci - 1);  // (ci is 16 or 32)
+  const float bl = p.b_loc[0], bs = p.b_ls[0];
+  constexpr int NF = LIKE_PIX / 4 / 16;  // 16-pixel fragments per wave
+  const int pw0 = chunk * LIKE_PIX + wave * (LIKE_PIX / 4);
+#pragma unroll 4
+  for (int t = 0; t < NF; ++t) {
+    const int px = pw0 + t * 16 + fr;
+    h16x8 bq;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bq[e] = (h16n_t)0.f;
+    if (px < npix) {
+      const int y = div32(px, p.d_w), x = px - y * p.w;
+      bq = *(const h16x8*)(vptr<h16_t>(p.hin, b, y, x) + coff);
+    }
+    const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4_t acc = mfma_h16(aw, bq, z, 0, 0, 0);
+    if (fg == 0) ps[wave * (LIKE_PIX / 4) + t * 16 + fr] = f2h_pk(acc[0] + bl, acc[1] + bs);
+  }
+  __syncthreads();
+  float acc = 0.f;
+  for (int i = 0; i < LIKE_PIX / 256; ++i) {
+    const int px = chunk * LIKE_PIX + i * 256 + tid;
+    if (px < npix) {
+      const int y = div32(px, p.d_w), x = px - y * p.w;
+      const uint32_t pk = ps[i * 256 + tid];
+      *(uint32_t*)vptr<h16_t>(p.params, b, y, x) = pk;
+      const float xv = Elem<h16_t>::ld(vptr<h16_t>(p.x, b, y, x));
+      acc -= dg_logp(h_lo(pk), h_hi(pk), xv);
+    }
+  }
+  const float tot = block_sum_256(acc, sm);
+  if (tid == 0) p.part[(int64_t)b * gridDim.x + chunk] = tot;
+}
+
+// Backward.  One block per split of the generic weight-gradient plan (wgrad_geometry: `pps` pixels, a multiple of 64).
+//   1. every pixel of the split: (g_loc, g_logscale) = dg_logp_grad, rounded to binary16 as dgauss_nll_bwd_kernel stores them,
+//      kept in LDS as f32 (zeros past the split's end) -- wgrad_kernel's gradient tile Gs, for all K-steps at once;
+//   2. per 64-pixel step: thread (pixel tid / 4, channels 8 (tid % 4) .. + 8) loads its 16 bytes of h, writes them to the
+//      activation tile Xs as f32 (wgrad_kernel's fill, same thread -> element mapping) and stores 16 bytes of grad(h):
+//        rn16( w_loc g_loc + f32(rn16(w_ls g_ls)) )
+//      -- the tape runs x_logscale's data gradient first (a plain store) and x_loc's second (accumulating on the stored value);
+//      each term is one exact binary16 x binary16 product added to the MFMA's zero accumulator (fmaf(w, g, +0): -0 becomes +0);
+//   3. the weight gradients as wgrad_kernel<h16, 1> forms them: v_mfma_f32_16x16x4f32 with pixels as K, waves 0 / 1 own input
+//      channels 0..15 / 16..31 over the first 32 pixels of the step and waves 2 / 3 the same over the last 32 (`kpart`), one
+//      accumulator per wave across all steps, the two K halves added in kpart order at the end.  Row 0 of the A operand is
+//      g_loc, row 1 g_logscale: both sites in one MFMA.  Bias: per step a = sum_r Gs[r] from zero in row order, bsum += a.
+#define DH_LDX 48
+union H8 { uint4 v4; h16_t e[8]; };  // eight binary16 values of one 16-byte group
+__global__ __launch_bounds__(256) void dgauss_head_bwd_kernel(DhP p) {
+  extern __shared__ __attribute__((aligned(16))) float dh_smem[];
+  __shared__ __attribute__((aligned(16))) float Xs[WG_PK * DH_LDX];
+  float* Gq = dh_smem;               // [pps][2]
+  float* bpart = dh_smem + 2 * p.pps;  // [pps / 64][2]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sp = blockIdx.x;
+  const int px0 = sp * p.pps, px1 = min(p.P, px0 + p.pps);
+  const int nstep = (px1 - px0 + WG_PK - 1) / WG_PK;
+  const int npix = p.h * p.w;
+
+  // ---- 1. the split's likelihood gradients
+  for (int i = tid; i < nstep * WG_PK; i += 256) {
+    const int m = px0 + i;
+    float gl = 0.f, gs = 0.f;
+    if (m < px1) {
+      const int n = div32(m, p.d_hw), rr = m - n * npix;
+      const int y = div32(rr, p.d_w), x = rr - y * p.w;
+      const uint32_t pk = *(const uint32_t*)vptr<h16_t>(p.params, n, y, x);
+      const float xv = Elem<h16_t>::ld(vptr<h16_t>(p.x, n, y, x));
+      const float coef = p.coef[(int64_t)n * p.coef_stride];
+      dg_logp_grad(h_lo(pk), h_hi(pk), xv, coef, gl, gs);
+      const uint32_t gk = f2h_pk(gl, gs);
+      if (p.gparams.p) *(uint32_t*)vptr<h16_t>(p.gparams, n, y, x) = gk;
+      gl = h_lo(gk); gs = h_hi(gk);
+    }
+    Gq[2 * i] = gl; Gq[2 * i + 1] = gs;
+  }
+  // lane constants of step 2: the weights of this thread's 8 channels
+  const int r = tid >> 2, cg = (tid & 3) * 8;
+  const bool chan = cg < p.ci;
+  float wl[8], ws[8];
+  {
+    H8 tl, ts;
+    tl.v4 = make_uint4(0, 0, 0, 0); ts.v4 = make_uint4(0, 0, 0, 0);
+    if (chan) { tl.v4 = *(const uint4*)(p.w_loc + cg); ts.v4 = *(const uint4*)(p.w_ls + cg); }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { wl[e] = h2f(tl.e[e]); ws[e] = h2f(ts.e[e]); }
+  }
+  __syncthreads();
+  if (tid < 2 * nstep) {  // bias: the per-step column sums, each from zero in row order
+    const int s = tid >> 1, col = tid & 1;
+    float a = 0.f;
+    for (int q = 0; q < WG_PK; ++q) a += Gq[2 * (s * WG_PK + q) + col];
+    bpart[tid] = a;
+  }
+
+  const int kpart = wave >> 1, jf = wave & 1;
+  f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < nstep; ++s) {
+    const int m = px0 + s * WG_PK + r;
+    H8 hv;
+    hv.v4 = make_uint4(0, 0, 0, 0);
+    const bool live = chan && m < px1;
+    int n = 0, y = 0, x = 0;
+    if (live) {
+      n = div32(m, p.d_hw);
+      const int rr = m - n * npix;
+      y = div32(rr, p.d_w); x = rr - y * p.w;
+      hv.v4 = *(const uint4*)(vptr<h16_t>(p.hin, n, y, x) + cg);
+    }
+    if (live) {
+      const float gl = Gq[2 * (s * WG_PK + r)], gs = Gq[2 * (s * WG_PK + r) + 1];
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = fmaf(wl[e], gl, 0.f) + h2f(f2h(fmaf(ws[e], gs, 0.f)));
+      uint4 ov;
+      ov.x = f2h_pk(o[0], o[1]); ov.y = f2h_pk(o[2], o[3]); ov.z = f2h_pk(o[4], o[5]); ov.w = f2h_pk(o[6], o[7]);
+      *(uint4*)(vptr<h16_t>(p.gh, n, y, x) + cg) = ov;
+    }
+    __syncthreads();  // the previous step's fragment reads of Xs are done
+    *(float4*)(Xs + r * DH_LDX + cg) = make_float4(h2f(hv.e[0]), h2f(hv.e[1]), h2f(hv.e[2]), h2f(hv.e[3]));
+    *(float4*)(Xs + r * DH_LDX + cg + 4) = make_float4(h2f(hv.e[4]), h2f(hv.e[5]), h2f(hv.e[6]), h2f(hv.e[7]));
+    __syncthreads();
+    const int kq0 = kpart * (WG_PK / 8);
+#pragma unroll
+    for (int k4 = kq0; k4 < kq0 + WG_PK / 8; ++k4) {
+      const int prow = k4 * 4 + (lane >> 4);
+      const float a = (lane & 15) < 2 ? Gq[2 * (s * WG_PK + prow) + (lane & 15)] : 0.f;
+      const float bq = Xs[prow * DH_LDX + jf * 16 + (lane & 15)];
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bq, acc, 0, 0, 0);
+    }
+  }
+
+  // ---- partials: the K halves combined in kpart order, as wgrad_kernel does
+  __syncthreads();
+  float* red = Xs;
+  if (kpart == 1) *(f32x4_t*)(red + (jf * 64 + lane) * 4) = acc;
+  __syncthreads();
+  if (kpart == 0) {
+    const f32x4_t o = *(const f32x4_t*)(red + (jf * 64 + lane) * 4);
+    acc[0] += o[0]; acc[1] += o[1];
+    const int ci = jf * 16 + (lane & 15);
+    if ((lane >> 4) == 0 && ci < p.ci) {
+      p.pw_loc[(size_t)sp * p.ci + ci] = acc[0];
+      p.pw_ls[(size_t)sp * p.ci + ci] = acc[1];
+    }
+  }
+  if (tid < 2) {
+    float bsum = 0.f;
+    for (int s = 0; s < nstep; ++s) bsum += bpart[2 * s + tid];
+    (tid == 0 ? p.pb_loc : p.pb_ls)[sp] = bsum;
   }
 }
 
@@ -846,6 +1041,74 @@ extern "C" int cgen_dgauss_nll_bwd(int32_t dtype, int32_t n, int32_t h, int32_t 
   if (dtype == CGEN_F32) hipLaunchKernelGGL(dgauss_nll_bwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(dgauss_nll_bwd_kernel<h16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   return check_launch("cgen_dgauss_nll_bwd");
+}
+
+#define DH_MAXPPS 4096  // pixels of a weight-gradient split the backward kernel keeps in LDS (32 KiB)
+
+// Shapes and layouts the fused head serves; fills the kernels' parameters.  `bwd`: the backward's operands are checked as well.
+static bool dgauss_head_fill(const cgen_dgauss_head_args* a, DhP& p, bool bwd) {
+  if (!a || a->dtype != CGEN_F16 || a->n < 1 || a->h < 1 || a->w < 1) return false;
+  const int ci = a->hin.c;
+  if ((ci != 16 && ci != 32) || a->params.c != 2 || a->x.c != 1) return false;
+  if (!a->hin.p || !a->params.p || !a->x.p || !a->img_loc || !a->img_ls || !a->bias_loc || !a->bias_ls) return false;
+  if ((int64_t)a->n * a->h * a->w >= (1ll << 31)) return false;
+  auto al4 = [](const cgen_view& v) { return (uintptr_t)v.p % 4 == 0 && v.sn % 2 == 0 && v.sh % 2 == 0 && v.sw % 2 == 0; };
+  if (!vec16_ok(a->hin, 2) || !al4(a->params) || (uintptr_t)a->img_loc % 16 != 0 || (uintptr_t)a->img_ls % 16 != 0) return false;
+  // the launches this one stands for must be the ones whose arithmetic it repeats: both head convs on conv_tile_kernel in one
+  // K-step (not the small-image kernel below its pixel threshold), the weight gradients on the generic kernel's plan
+  cgen_conv_args c;
+  memset(&c, 0, sizeof(c));
+  c.dtype = CGEN_F16; c.n = a->n; c.h = a->h; c.w = a->w; c.ks = 1; c.nseg = 1;
+  c.seg[0] = a->hin; c.weight = a->img_loc; c.bias = a->bias_loc;
+  c.out = a->params; c.out.c = 1;
+  if (!conv_is_tile_1x1_onestep(&c)) return false;
+  c.out.p = (char*)a->params.p + 2; c.weight = a->img_ls; c.bias = a->bias_ls;
+  if (!conv_is_tile_1x1_onestep(&c)) return false;
+  cgen_wgrad_args wa;
+  memset(&wa, 0, sizeof(wa));
+  wa.dtype = CGEN_F16; wa.n = a->n; wa.h = a->h; wa.w = a->w; wa.ks = 1; wa.nseg = 1;
+  wa.seg[0] = a->hin; wa.gout = a->params; wa.gout.c = 1;  // (the gradient of the parameter tensor has its layout)
+  int32_t kind = -1;
+  const int nsplit_plan = cgen_conv2d_wgrad_plan(&wa, &kind);
+  if (kind != 0) return false;
+  memset(&p, 0, sizeof(p));
+  p.n = a->n; p.h = a->h; p.w = a->w; p.ci = ci; p.P = a->n * a->h * a->w;
+  wgrad_geometry(p.P, 1, 1, 1, p.nsplit, p.pps);
+  if (p.nsplit != nsplit_plan || p.pps > DH_MAXPPS) return false;
+  p.d_hw = mk_div32((uint32_t)(a->h * a->w)); p.d_w = mk_div32((uint32_t)a->w);
+  p.hin = mk(a->hin); p.params = mk(a->params); p.x = mk(a->x);
+  p.w_loc = (const h16_t*)a->img_loc; p.w_ls = (const h16_t*)a->img_ls; p.b_loc = a->bias_loc; p.b_ls = a->bias_ls;
+  p.part = a->nll_part;
+  if (bwd) {
+    if (!a->coef_dev || !a->g_h.p || a->g_h.c != ci || !vec16_ok(a->g_h, 2) || (a->g_params.p && (a->g_params.c != 2 || !al4(a->g_params)))) return false;
+    if (a->nsplit != p.nsplit || !a->partial_w_loc || !a->partial_b_loc || !a->partial_w_ls || !a->partial_b_ls) return false;
+    p.coef = a->coef_dev; p.coef_stride = a->coef_stride; p.gh = mk(a->g_h); p.gparams = mk(a->g_params);
+    p.pw_loc = a->partial_w_loc; p.pb_loc = a->partial_b_loc; p.pw_ls = a->partial_w_ls; p.pb_ls = a->partial_b_ls;
+  }
+  return true;
+}
+
+extern "C" int cgen_dgauss_head_supported(const cgen_dgauss_head_args* a) {
+  DhP p;
+  return dgauss_head_fill(a, p, false) ? 1 : 0;
+}
+
+extern "C" int cgen_dgauss_head_fwd(const cgen_dgauss_head_args* a, cgen_stream_t stream) {
+  DhP p;
+  if (!dgauss_head_fill(a, p, false) || !a->nll_part)
+    return fail(CGEN_EUNSUPPORTED, "cgen_dgauss_head_fwd: not served (ask cgen_dgauss_head_supported first)");
+  dim3 grid(cgen_like_chunks(p.h, p.w), p.n);
+  hipLaunchKernelGGL(dgauss_head_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+  return check_launch("cgen_dgauss_head_fwd");
+}
+
+extern "C" int cgen_dgauss_head_bwd(const cgen_dgauss_head_args* a, cgen_stream_t stream) {
+  DhP p;
+  if (!dgauss_head_fill(a, p, true))
+    return fail(CGEN_EUNSUPPORTED, "cgen_dgauss_head_bwd: not served, or the backward operands do not fit the plan (nsplit %d)", a ? a->nsplit : -1);
+  const size_t lds = (size_t)(2 * p.pps + 2 * (p.pps / WG_PK)) * sizeof(float);
+  hipLaunchKernelGGL(dgauss_head_bwd_kernel, dim3(p.nsplit), dim3(256), lds, (hipStream_t)stream, p);
+  return check_launch("cgen_dgauss_head_bwd");
 }
 
 extern "C" int cgen_dgauss_sample(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, cgen_view params, float logt,

@@ -9,14 +9,14 @@
 
 #include "conv_shared.h"
 #include "wgrad3.h"
+#include "like_head.h"
 
 namespace cgen {
 
 // ============================================================================= weight gradient
 // dW[co][tap][ci] = sum_px G[px][co] * act(X)[px + tap][ci]          (f32 MFMA 16x16x4 for both storage dtypes)
 // Workgroup tile: (16*NTC output channels) x (32 input channels) x (<= 9 taps) x one pixel split.
-#define WG_PK 64
-#define WG_MAXT 9
+// (WG_PK = 64 pixels per K-step, WG_MAXT = 9 taps, and the split geometry: like_head.h)
 
 struct WgP {
   int N, H, W, KS, pad, nseg, act, Co, P, taps, ci_total, nsplit, pix_per_split, n_tapgroups, n_cichunks;
@@ -649,19 +649,6 @@ static void launch_wgrad2_ks(const Wg2P& p, const Wg2Geom& g, hipStream_t st) {
     if (!once1) { (void)hipFuncSetAttribute((const void*)wgrad_tile_kernel<NCF, NJW, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); once1 = true; }
     hipLaunchKernelGGL((wgrad_tile_kernel<NCF, NJW, 1>), grid, block, g.lds, st, p);
   }
-}
-
-static inline int wgrad_ntc(int co) { return co <= 16 ? 1 : (co <= 32 ? 2 : 4); }
-
-static void wgrad_geometry(int P, int co, int ci_chunks, int ks, int& nsplit, int& pps) {
-  const int ntc = wgrad_ntc(co);
-  const int tiles = ci_chunks * ceil_div(co, ntc * 16) * ceil_div(ks * ks, WG_MAXT);
-  int want = ceil_div(2048, tiles);
-  int maxs = ceil_div(P, 4 * WG_PK);
-  nsplit = want < 1 ? 1 : (want > maxs ? maxs : want);
-  if (nsplit < 1) nsplit = 1;
-  pps = pad_to(ceil_div(P, nsplit), WG_PK);
-  nsplit = ceil_div(P, pps);
 }
 
 template <typename T>

@@ -342,6 +342,12 @@ class Engine(WgradMixin):
         self.lat_tail_fwd = os.environ.get("CGEN_LAT_TAIL_FWD", "1") != "0"
         self.lat_tail_fwd_minpx = int(os.environ.get("CGEN_LAT_TAIL_FWD_MINPX", "0"))  # layers with fewer pixels (n * h * w) keep the three launches
         self.lat_tails_fwd = 0  # fused forward launches since begin()
+        # The discretised-Gaussian likelihood head of a recorded pass -- the 1x1 convs x_loc / x_logscale and the NLL around them -- as
+        # one launch each way (cgen_dgauss_head_fwd / _bwd; like_head_fwd / _bw_like_head below): the bits of the three forward and
+        # the six backward launches it stands for, ONE tape entry.  0: those launches.
+        self.like_head = os.environ.get("CGEN_LIKE_HEAD", "1") != "0"
+        self.like_heads = 0  # fused head launches (either way) since begin()
+        self.like_coef_ptr = None  # device pointer of the NLL's per-sample backward coefficient (HVAE._run_backward sets it)
         self.wgrad_bg_wgs = int(os.environ.get("CGEN_WGRAD_BG_WGS", "304"))
         self.wgrad_bg_reduce = os.environ.get("CGEN_WGRAD_BG_REDUCE", "1") != "0"
         self._wg_cum, self._wg_total, self._wg_nflush = 0.0, 0.0, 0
@@ -445,6 +451,7 @@ class Engine(WgradMixin):
         self._split_done = False
         self.passes = 0
         self.lat_tails_fwd = 0
+        self.like_heads = 0
         self.stream = torch.cuda.current_stream(self.device).cuda_stream
 
     def new(self, n, h, w, c, rg=True, es=None, rem=False):
@@ -1293,6 +1300,72 @@ class Engine(WgradMixin):
                 (self.tape if tape_hold is None else tape_hold).append((self._bw_conv, (site_f, [z, p_feat], ACT_NONE, zf, None, None), 0))
         return z, h2, zf
 
+    def _like_head_args(self, site_loc, site_ls, h, params, x):
+        t = _lib.DgaussHeadArgs()
+        t.dtype, t.n, t.h, t.w = self.dt, h.n, h.h, h.w
+        t.hin, t.params, t.x = h.cv(), params, x.cv()
+        t.img_loc, t.img_ls = site_loc.img_fwd, site_ls.img_fwd
+        bl, bs = site_loc.conv.bias, site_ls.conv.bias
+        t.bias_loc, t.bias_ls = (bl.data_ptr() if bl is not None else None), (bs.data_ptr() if bs is not None else None)
+        return t
+
+    def like_head_fwd(self, site_loc, site_ls, h, x, nll_count):
+        """conv(x_loc, [h]) and conv(x_logscale, [h]) into the two channels of one parameter tensor, then dgauss_nll_fwd of it
+        against `x` into `nll_count` fresh f32 partials, as ONE launch on the current stream with the three launches' bits
+        (cgen_dgauss_head_fwd), and one tape entry whose backward is one launch as well (_bw_like_head).  Returns (parameter
+        tensor, pointer to the partials), or None -- nothing done, the caller runs the three launches -- when the pass is not
+        recorded (inference keeps the convs), the kernel does not serve the shape, a head is not a plain trainable 1x1 conv with
+        bias, per-site timing is on, or under CGEN_ABLATE."""
+        if not self.like_head or not self.recording or self.dt != F16 or self.prof is not None or self._ablate:
+            return None
+        for st in (site_loc, site_ls):
+            cv = st.conv
+            if (st.ks != 1 or st.co != 1 or list(st.seg_c) != [h.c] or cv.bias is None or not cv.weight.requires_grad
+                    or not cv.bias.requires_grad):
+                return None
+        if h.rem or not h.rg or x.c != 1 or (x.n, x.h, x.w) != (h.n, h.h, h.w) or id(h.base) in self.grads:
+            return None
+        cp = 8  # (probe view for _supported(): the layout new() will give the parameter tensor, at a pointer with the arena's alignment)
+        t = self._like_head_args(site_loc, site_ls, h, View(h.base.ptr, h.h * h.w * cp, h.w * cp, cp, 2, 0), x)
+        if not self.lib.dgauss_head_supported(C.byref(t)):
+            return None
+        params = self.new(h.n, h.h, h.w, 2)
+        nll_ptr = self.new_f32(nll_count)
+        t.params, t.nll_part = params.cv(), nll_ptr
+        self.lib.dgauss_head_fwd(C.byref(t), self.stream)
+        self.like_heads += 1
+        if self._dbg_names is not None:
+            self._dbg_names[id(params.base)] = site_loc.name
+        self.tape.append((self._bw_like_head, (site_loc, site_ls, h, params, x), self._bw_tag))
+        return params, nll_ptr
+
+    def _bw_like_head(self, site_loc, site_ls, h, params, x):
+        """Backward of like_head_fwd's entry as one launch (cgen_dgauss_head_bwd): the NLL's gradient with respect to the parameter
+        tensor (used rounded to binary16, never stored: nothing else reads it), grad(h) with the rounding points of the two data
+        gradients in tape order, and the split-K partials of both heads' weight and bias gradients in the buffers, the layout and
+        the split count _wgrad plans.  The two sites are registered as weight-gradient events like any other (reductions, the
+        data-parallel early_final set) and their cost moves the flush marks as before; they never enter the deferred batch."""
+        gv, _, acc = self._dgrad_target(h)
+        assert not acc, "the likelihood heads are the first readers of the decoder's last tensor"
+        t = self._like_head_args(site_loc, site_ls, h, params.cv(), x)
+        t.coef_dev, t.coef_stride, t.g_h, t.g_params = self.like_coef_ptr, 0, gv.cv(), NULL_VIEW
+        plans = []
+        for k, st in ((1, site_ls), (0, site_loc)):  # (tape order: x_logscale's backward runs first)
+            g = View(params.ptr + k * params.es, params.sn, params.sh, params.sw, 1, 0)  # the layout its grad_out slice would have
+            plans.append((st,) + self._wgrad_plan(st, [h], ACT_NONE, g))
+        (_, a_ls, key_ls, ns_ls), (_, a_loc, key_loc, ns_loc) = plans
+        assert ns_ls == ns_loc
+        t.nsplit = ns_loc
+        t.partial_w_loc, t.partial_b_loc, t.partial_w_ls, t.partial_b_ls = a_loc.partial_w, a_loc.partial_b, a_ls.partial_w, a_ls.partial_b
+        self.lib.dgauss_head_bwd(C.byref(t), self.stream)
+        self.launches += 1
+        self.like_heads += 1
+        for st, _, key, nsplit in plans:
+            self._wg_events.append((st, key, nsplit))
+            if self._defer_wgrad():
+                self._wg_cum += 2.0 * st.ci * st.taps * st.co * h.n * h.h * h.w
+                self._wgrad_marks()
+
     def sample_gaussian(self, loc, ls, eps, stream_id, logt):
         z = self.new(loc.n, loc.h, loc.w, loc.c)
         self.lib.sample_gaussian(self.dt, z.n, z.h, z.w, z.c, loc.cv(), ls.cv(), eps.cv() if eps is not None else NULL_VIEW,
@@ -1615,6 +1688,9 @@ class Engine(WgradMixin):
         """(conv site, a tensor of its image size) of every conv that tape entry (fn, a, tag) runs the backward of."""
         if fn == self._bw_conv:
             yield a[0], a[1][0]
+        elif fn == self._bw_like_head:
+            yield a[1], a[2]
+            yield a[0], a[2]
         elif fn == self._bw_block3 or fn == self._bw_block4:
             for st in a.sites:
                 yield st, a.segs[0]

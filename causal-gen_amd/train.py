@@ -184,8 +184,12 @@ class TrainStep:
             m.__dict__["_beta_dev"] = None
         params, xin, B, R, Cx, dims = m.__dict__["_saved"]
         eng.kl_coef_ptr = self.coef.data_ptr() + 4
-        gparams = eng.seed_grad(params)
-        if getattr(m.likelihood, "logit_space", False):
+        eng.like_coef_ptr = self.coef.data_ptr()
+        fused = m.__dict__.get("_like_fused", False)
+        gparams = None if fused else eng.seed_grad(params)
+        if fused:  # the head's tape entry runs the NLL's backward itself, with like_coef_ptr (engine._bw_like_head)
+            pass
+        elif getattr(m.likelihood, "logit_space", False):
             u, snap = m.__dict__["_gauss_noise"][:2]
             self.lib.gauss_nll_bwd(eng.dt, B, R, R, Cx, params.cv(), xin.cv(), u, snap.data_ptr(), 977, self.coef.data_ptr(), 0,
                                    gparams.cv(), eng.stream)

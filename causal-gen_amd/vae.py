@@ -919,14 +919,22 @@ class HVAE(nn.Module):
             col = S.sum(0)
             torch.distributed.all_reduce(col)
             S.copy_((col / float(B * world)).expand(B, ncol))
-        params = self._likelihood_params(eng, h)
-        nchunk = lib.like_chunks(R, R)
-        nll_ptr = eng.new_f32(B * nchunk)
         lk = self.likelihood
-        if lk.kind == "dgauss":
-            lib.dgauss_nll_fwd(eng.dt, B, R, R, Cx, params.cv(), xin.cv(), nll_ptr, eng.stream)
-        else:
-            lib.dmol_nll_fwd(eng.dt, B, R, R, params.cv(), xin.cv(), nll_ptr, eng.stream)
+        nchunk = lib.like_chunks(R, R)
+        params = None
+        if lk.kind == "dgauss" and Cx == 1 and eng.recording and not getattr(lk, "logit_space", False):
+            # a recorded pass: both heads and the NLL in one launch, one tape entry (engine.like_head_fwd; CGEN_LIKE_HEAD=0: never)
+            fused = eng.like_head_fwd(self._site(eng, lk.x_loc), self._site(eng, lk.x_logscale), h, xin, B * nchunk)
+            if fused is not None:
+                params, nll_ptr = fused
+        self.__dict__["_like_fused"] = params is not None
+        if params is None:
+            params = self._likelihood_params(eng, h)
+            nll_ptr = eng.new_f32(B * nchunk)
+            if lk.kind == "dgauss":
+                lib.dgauss_nll_fwd(eng.dt, B, R, R, Cx, params.cv(), xin.cv(), nll_ptr, eng.stream)
+            else:
+                lib.dmol_nll_fwd(eng.dt, B, R, R, params.cv(), xin.cv(), nll_ptr, eng.stream)
         out3 = torch.empty(3, dtype=torch.float32, device=eng.device)
         dims = float(Cx * R * R)
         if fb is None:
@@ -1048,8 +1056,12 @@ class HVAE(nn.Module):
         self.__dict__["_coef"] = coef
         eng.stream = torch.cuda.current_stream(eng.device).cuda_stream
         eng.kl_coef_ptr = coef.data_ptr() + 4
-        gparams = eng.seed_grad(params)
-        if getattr(self.likelihood, "logit_space", False):  # simple_vae's GaussNet: same dequantisation noise as the forward pass
+        eng.like_coef_ptr = coef.data_ptr()
+        fused = self.__dict__.get("_like_fused", False)
+        gparams = None if fused else eng.seed_grad(params)
+        if fused:  # the head's tape entry runs the NLL's backward itself, with like_coef_ptr (engine._bw_like_head): no seed, no launch
+            eng.launches -= 1  # (the count below)
+        elif getattr(self.likelihood, "logit_space", False):  # simple_vae's GaussNet: same dequantisation noise as the forward pass
             u, snap = self.__dict__["_gauss_noise"][:2]
             lib.gauss_nll_bwd(eng.dt, B, R, R, Cx, params.cv(), xin.cv(), u, snap.data_ptr(), 977, coef.data_ptr(), 0, gparams.cv(),
                               eng.stream)

@@ -75,14 +75,22 @@ class WgradMixin:
         b = site.conv.bias
         return site.conv.weight.requires_grad or (b is not None and b.requires_grad)
 
-    def _wgrad(self, site, segs, act, g):
+    def _wgrad_plan(self, site, segs, act, g):
+        """The launch arguments of one weight gradient with its split-K partial buffer planned and attached: (args, the key of the
+        buffer in _partials, split count).  `g`: grad_out as a tensor, or a ready View of its layout (a 1x1 site on an image of
+        5 x 5 or more: the fused likelihood head, which never materialises it)."""
         x0 = segs[0]
         a = _lib.WgradArgs()
-        gn, gh, gw, vw = self._geom(site.ks, list(segs) + [g])
+        if isinstance(g, _lib.View):
+            gn, gh, gw, vw = self._geom(site.ks, list(segs))
+            assert (gn, gh, gw) == (x0.n, x0.h, x0.w)
+            a.gout = g
+        else:
+            gn, gh, gw, vw = self._geom(site.ks, list(segs) + [g])
+            a.gout = vw(g)
         a.dtype, a.n, a.h, a.w, a.ks, a.nseg, a.act = self.dt, gn, gh, gw, site.ks, len(segs), act
         for k, s in enumerate(segs):
             a.seg[k] = vw(s)
-        a.gout = vw(g)
         use = sum(1 for e in self._wg_events if e[0] is site)
         # (the plan -- kernel, split count, partial LAYOUT -- also depends on how the views are laid out: strides and 16-byte alignment
         #  decide between the streaming, tiled and generic kernels.  They are part of the key, so a differently laid-out view of the
@@ -101,6 +109,11 @@ class WgradMixin:
         a.nsplit = nsplit
         a.partial_w = buf.data_ptr()
         a.partial_b = buf.data_ptr() + 4 * nsplit * nw if site.conv.bias is not None else None
+        return a, key, nsplit
+
+    def _wgrad(self, site, segs, act, g):
+        x0 = segs[0]
+        a, key, nsplit = self._wgrad_plan(site, segs, act, g)
         if self._defer_wgrad():
             cost = 2.0 * site.ci * site.taps * site.co * x0.n * x0.h * x0.w
             self._wg_deferred.append((a, cost))

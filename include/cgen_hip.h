@@ -527,6 +527,43 @@ int cgen_dgauss_nll_fwd(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t 
 /* g_params = coef_dev[b*coef_stride] * d(sum -log p)/d params */
 int cgen_dgauss_nll_bwd(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, cgen_view params, cgen_view x,
                         const float* coef_dev, int32_t coef_stride, cgen_view g_params, cgen_stream_t);
+/* The two 1x1 likelihood heads x_loc / x_logscale (vae.py:325-333) fused with the discretised-Gaussian NLL, for one input
+ * channel (C = 1) on the CGEN_F16 path: one launch each way, bit-identical to the launches it stands for.
+ *   cgen_dgauss_head_fwd = cgen_conv2d(hin -> params channel 0, img_loc, bias_loc) + cgen_conv2d(hin -> params channel 1, img_ls,
+ *     bias_ls) + cgen_dgauss_nll_fwd(params, x -> nll_part): reads hin once.
+ *   cgen_dgauss_head_bwd = cgen_dgauss_nll_bwd(-> g_params) + the data gradient of x_logscale into g_h (a store) + the data gradient
+ *     of x_loc accumulating on it + cgen_conv2d_wgrad of both heads (partials in the layout and split count of
+ *     cgen_conv2d_wgrad_plan, `nsplit`): reads hin, params and x once and writes g_h once.  g_params is optional (p == NULL: the
+ *     rounded gradients are used but not stored).
+ * img_loc / img_ls: the heads' forward images from cgen_weight_prep (mode 0; row 0 is read); both biases are required.
+ * Served (cgen_dgauss_head_supported() == 1, answered without a GPU, looks at dtype, n, h, w, hin, params, x, the images and the
+ * biases): CGEN_F16; hin.c 16 or 32, 16-byte aligned; params.c == 2 and x.c == 1; and a shape at which cgen_conv2d serves the two
+ * head convs with its halo-tiled kernel in one K-step (h, w >= 5 and more pixels than the small-image kernel takes) and the
+ * weight gradients run on the generic kernel's plan.  Anything else: 0, and the entry points return CGEN_EUNSUPPORTED. */
+typedef struct cgen_dgauss_head_args {
+  int32_t dtype, n, h, w;
+  cgen_view hin;
+  const void* img_loc;
+  const void* img_ls;
+  const float* bias_loc;
+  const float* bias_ls;
+  cgen_view params;
+  cgen_view x;
+  float* nll_part; /* forward: [n][cgen_like_chunks(h, w)] */
+  /* backward only */
+  const float* coef_dev; /* as in cgen_dgauss_nll_bwd */
+  int32_t coef_stride;
+  int32_t nsplit;        /* cgen_conv2d_wgrad_plan of either head's weight gradient */
+  cgen_view g_h;
+  cgen_view g_params;    /* optional */
+  float* partial_w_loc;  /* [nsplit][1][1][hin.c] */
+  float* partial_b_loc;  /* [nsplit][1] */
+  float* partial_w_ls;
+  float* partial_b_ls;
+} cgen_dgauss_head_args;
+int cgen_dgauss_head_supported(const cgen_dgauss_head_args* a);
+int cgen_dgauss_head_fwd(const cgen_dgauss_head_args* a, cgen_stream_t stream);
+int cgen_dgauss_head_bwd(const cgen_dgauss_head_args* a, cgen_stream_t stream);
 /* DGaussNet.sample (vae.py:413-422): loc (RGB autoregressive on the clamped predicted channels) and exp(logscale + log t),
  * NCHW f32 out.  rng == NULL: return_loc=True (x = clamp(loc)); rng = device (seed, offset): return_loc=False,
  * x = clamp(loc + scale * N(0,1)) with Philox noise of stream `stream_id` */
