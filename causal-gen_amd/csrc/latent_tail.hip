@@ -15,6 +15,8 @@
 //     every result leaves as one 16-byte store (by default after the roundings the four launches applied on the way: ORDER below);
 //   * gridDim.y splits the output rows: part 0 owns g_z (K = g_f.c + C, never stored) and runs the reparam epilogue, parts
 //     1.. own LT_NP 32-channel blocks of g_pfeat each (K = g_f.c; the identity G_h -> g_pfeat is an add in the epilogue).
+// Both entry points also take a DETERMINISTIC layer (z = p_loc; called without q_loc / q_ls): DET instances of the same bodies,
+// kernels of their own (latent_tail_det1_bwd_kernel: one workgroup row, C <= 64; latent_tail_det_bwd_kernel; latent_tail_det_fwd_kernel).
 #include <stdlib.h>
 
 #include "common.h"
@@ -75,8 +77,11 @@ __device__ __forceinline__ f32x4_t lt_sum(const f32x4_t (&a)[NPART][2], int h) {
 //      order) and rounded to binary16 wherever that path stores a tensor: grad(z) after each of its two writers, grad(p_feat) before
 //      the residual is added.
 // ---- part 0: g_z = [W_f[:, :Z]^T | W_p[:, :Z]^T] [G_f ; G_h] (+ gz_in) in registers, then the reparam / KL backward
-template <int MAXKF, bool ACC, int ORDER>
+// DET: the layer is deterministic (z = p_loc; no reparam entry, no posterior): g_z IS grad(p_loc), the p_ls channels of out_p leave as
+// zeros (nobody else writes them: the launch owns the whole 2Z + C pixel) and nothing of the reparam operands is loaded.
+template <int MAXKF, bool ACC, int ORDER, bool DET = false>
 __device__ __forceinline__ void lt_run_z(const LtP& p, char* smem) {
+  static_assert(!(DET && ACC), "the deterministic tail does not accumulate");
   constexpr int NPART = ORDER == 2 ? 4 : 1;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
   const int nks = p.nks_f + p.nks_h, K = nks * 32, ldw = K + 8, Kf = p.nks_f * 32;
@@ -100,9 +105,11 @@ __device__ __forceinline__ void lt_run_z(const LtP& p, char* smem) {
     for (int i = 0; i < MAXKF; ++i) {
       if (i < p.nks_h) xh[i] = *(const uint4*)(p.g_h + (pc * p.s_gh + i * 32 + ch));
     }
-    ql = lt_ld(p.q_loc, pc * p.s_ql + ch, ok); qs = lt_ld(p.q_ls, pc * p.s_qs + ch, ok);
-    pl = lt_ld(p.p_loc, pc * p.s_pl + ch, ok); ps = lt_ld(p.p_ls, pc * p.s_ps + ch, ok);
-    zv = lt_ld(p.z, pc * p.s_z + ch, ok);
+    if constexpr (!DET) {
+      ql = lt_ld(p.q_loc, pc * p.s_ql + ch, ok); qs = lt_ld(p.q_ls, pc * p.s_qs + ch, ok);
+      pl = lt_ld(p.p_loc, pc * p.s_pl + ch, ok); ps = lt_ld(p.p_ls, pc * p.s_ps + ch, ok);
+      zv = lt_ld(p.z, pc * p.s_z + ch, ok);
+    }
     if constexpr (ACC) {  // (the instance without them keeps 20 registers fewer: one more workgroup per CU)
       gzi = lt_ld(p.gz_in, pc * p.s_gz + ch, ok && has_gz);
       pq1 = lt_ld(p.out_q, pc * p.s_oq + ch, ok && p.acc_q); pq2 = lt_ld(p.out_q, pc * p.s_oq + p.Z + ch, ok && p.acc_q);
@@ -165,30 +172,35 @@ __device__ __forceinline__ void lt_run_z(const LtP& p, char* smem) {
           else gz[e] = has_gz ? lt_r16(zh + tp[e]) : lt_r16(zh);
         }
       }
-      unpack8(ql, fql); unpack8(qs, fqs); unpack8(pl, fpl); unpack8(ps, fps); unpack8(zv, fz);
-      const int b = px / p.hw;
-      const float k0 = p.coef[(int64_t)b * p.coef_stride];
-      reparam_kl_bwd_vec8_math(k0, p.chan_scale, ch, p.logt, true, fql, fqs, fpl, fps, gz, fz, o1, o2, o3, o4);
-      if (ACC && p.acc_q) {
-        unpack8(pq1, tp);
+      if constexpr (DET) {  // grad(p_loc) = g_z (already rounded as the launches round it), grad(p_ls) = 0
+        *(uint4*)(p.out_p + (px * p.s_op + ch)) = pack8(gz);
+        *(uint4*)(p.out_p + (px * p.s_op + p.Z + ch)) = make_uint4(0, 0, 0, 0);
+      } else {
+        unpack8(ql, fql); unpack8(qs, fqs); unpack8(pl, fpl); unpack8(ps, fps); unpack8(zv, fz);
+        const int b = px / p.hw;
+        const float k0 = p.coef[(int64_t)b * p.coef_stride];
+        reparam_kl_bwd_vec8_math(k0, p.chan_scale, ch, p.logt, true, fql, fqs, fpl, fps, gz, fz, o1, o2, o3, o4);
+        if (ACC && p.acc_q) {
+          unpack8(pq1, tp);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o1[e] += tp[e];
-        unpack8(pq2, tp);
+          for (int e = 0; e < 8; ++e) o1[e] += tp[e];
+          unpack8(pq2, tp);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o2[e] += tp[e];
+          for (int e = 0; e < 8; ++e) o2[e] += tp[e];
+        }
+        if (ACC && p.acc_p) {
+          unpack8(pp1, tp);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o3[e] += tp[e];
+          unpack8(pp2, tp);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o4[e] += tp[e];
+        }
+        *(uint4*)(p.out_q + (px * p.s_oq + ch)) = pack8(o1);
+        *(uint4*)(p.out_q + (px * p.s_oq + p.Z + ch)) = pack8(o2);
+        *(uint4*)(p.out_p + (px * p.s_op + ch)) = pack8(o3);
+        *(uint4*)(p.out_p + (px * p.s_op + p.Z + ch)) = pack8(o4);
       }
-      if (ACC && p.acc_p) {
-        unpack8(pp1, tp);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o3[e] += tp[e];
-        unpack8(pp2, tp);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o4[e] += tp[e];
-      }
-      *(uint4*)(p.out_q + (px * p.s_oq + ch)) = pack8(o1);
-      *(uint4*)(p.out_q + (px * p.s_oq + p.Z + ch)) = pack8(o2);
-      *(uint4*)(p.out_p + (px * p.s_op + ch)) = pack8(o3);
-      *(uint4*)(p.out_p + (px * p.s_op + p.Z + ch)) = pack8(o4);
     }
     t += (int)gridDim.x;
     if (t >= p.ntiles) break;
@@ -298,12 +310,166 @@ __global__ __launch_bounds__(256, ORDER == 2 ? 2 : (ACC ? 3 : 4)) void latent_ta
   else lt_run_p<MAXKF, ACC, ORDER>(p, lt_smem);
 }
 
+// ---- the deterministic layer with C, g_f.c <= 64 (every preset's) in ONE workgroup row: g_z and g_pfeat from the same fragments.
+// The two-row split reads both gradient tensors once per row and writes each half of a pixel's 2Z + C channels at another time; here a
+// wave loads its 16 pixels of G_f and G_h once -- K-step pr of G_h IS the epilogue operand of g_pfeat's block pr (lane group fg holds
+// channels 32 pr + 8 fg .. + 8 either way) -- and stores the whole pixel.  LDS: the z slab [32][K_z + 8], then the p_feat slab
+// [32 nb][K_f + 8].  Same sums, same roundings as lt_run_z<DET> / lt_run_p.
+#define LT_DK 2  // K-steps per gradient tensor (and 32-channel blocks of g_pfeat) of the one-row instance
+template <int ORDER>
+__device__ __forceinline__ void lt_run_det1(const LtP& p, char* smem) {
+  static_assert(ORDER == 0 || ORDER == 1, "the sequential orders only");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fg = lane >> 4;
+  const int Kf = p.nks_f * 32, K = Kf + p.nks_h * 32, ldz = K + 8, ldp = Kf + 8, nb = p.nks_h;
+  const int ch = fg * 8;
+  const bool live = ch < p.Z;
+  char* smem_p = smem + 32 * ldz * 2;
+
+  uint4 xf[LT_DK], xh[LT_DK];
+  int px = 0;
+  bool inside = false;
+  auto request = [&](int t) {
+    px = t * LT_PX + wave * 16 + fr;
+    inside = px < p.P;
+    const int pc = inside ? px : p.P - 1;  // (a lane past the last pixel multiplies the last pixel again; nothing of it is stored)
+#pragma unroll
+    for (int i = 0; i < LT_DK; ++i) {
+      if (i < p.nks_f) xf[i] = *(const uint4*)(p.g_f + (pc * p.s_gf + i * 32 + ch));
+    }
+#pragma unroll
+    for (int i = 0; i < LT_DK; ++i) {
+      if (i < p.nks_h) xh[i] = *(const uint4*)(p.g_h + (pc * p.s_gh + i * 32 + ch));
+    }
+  };
+  int t = (int)blockIdx.x;
+  request(t);
+  {  // the two slabs, once: rows permuted as in lt_run_z / lt_run_p
+    const int gz = K >> 3, gp = Kf >> 3;
+    for (int g = tid; g < 32 * gz; g += 256) {
+      const int r = g / gz, k = (g - r * gz) * 8;
+      const int h = r >> 4, j = r & 15, c = (j >> 2) * 8 + h * 4 + (j & 3);
+      const h16_t* src = k < Kf ? p.img_fz + (c * p.krow_f + k) : p.img_pz + (c * p.krow_p + (k - Kf));
+      *(uint4*)(smem + (r * ldz + k) * 2) = lt_ld(src, 0, c < p.Z);
+    }
+    for (int g = tid; g < nb * 32 * gp; g += 256) {
+      const int r = g / gp, k = (g - r * gp) * 8;
+      const int pr = r >> 5, h = (r >> 4) & 1, j = r & 15, c = pr * 32 + (j >> 2) * 8 + h * 4 + (j & 3);
+      *(uint4*)(smem_p + (r * ldp + k) * 2) = *(const uint4*)(p.img_fp + (c * p.krow_f + k));  // (c < C: nb blocks of 32)
+    }
+  }
+  __syncthreads();
+  const char* az = smem + (fr * ldz + fg * 8) * 2;
+  const char* azh = az + Kf * 2;
+  const char* ap = smem_p + (fr * ldp + fg * 8) * 2;
+  for (;;) {
+    f32x4_t aF[2], aH[2], aP[LT_DK][2];
+    aF[0] = aF[1] = aH[0] = aH[1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int pr = 0; pr < LT_DK; ++pr) aP[pr][0] = aP[pr][1] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < LT_DK; ++i) {
+      if (i < p.nks_f) {  // (uniform)
+        const h16x8 b = lt_frag(xf[i]);
+        aF[0] = mfma_h16(*(const h16x8*)(az + i * 64), b, aF[0], 0, 0, 0);
+        aF[1] = mfma_h16(*(const h16x8*)(az + (16 * ldz) * 2 + i * 64), b, aF[1], 0, 0, 0);
+#pragma unroll
+        for (int pr = 0; pr < LT_DK; ++pr) {
+          if (pr < nb) {  // (uniform)
+            aP[pr][0] = mfma_h16(*(const h16x8*)(ap + ((pr * 32) * ldp) * 2 + i * 64), b, aP[pr][0], 0, 0, 0);
+            aP[pr][1] = mfma_h16(*(const h16x8*)(ap + ((pr * 32 + 16) * ldp) * 2 + i * 64), b, aP[pr][1], 0, 0, 0);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < LT_DK; ++i) {
+      if (i < p.nks_h) {  // (uniform; ORDER 0 goes on with the one sum)
+        const h16x8 b = lt_frag(xh[i]);
+        f32x4_t(&a)[2] = ORDER == 0 ? aF : aH;
+        a[0] = mfma_h16(*(const h16x8*)(azh + i * 64), b, a[0], 0, 0, 0);
+        a[1] = mfma_h16(*(const h16x8*)(azh + (16 * ldz) * 2 + i * 64), b, a[1], 0, 0, 0);
+      }
+    }
+    if (inside) {
+      h16_t* o = p.out_p + px * p.s_op;
+      if (live) {  // grad(p_loc) = g_z, grad(p_ls) = 0
+        float gz[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float zf = e < 4 ? aF[0][e & 3] : aF[1][e & 3], zh = e < 4 ? aH[0][e & 3] : aH[1][e & 3];
+          if constexpr (ORDER == 0) gz[e] = zf;
+          else gz[e] = p.nks_f ? lt_r16(zh + lt_r16(zf)) : lt_r16(zh);  // z_feat_proj's data gradient wrote grad(p_loc), z_proj's added to it
+        }
+        *(uint4*)(o + ch) = pack8(gz);
+        *(uint4*)(o + p.Z + ch) = make_uint4(0, 0, 0, 0);
+      }
+#pragma unroll
+      for (int pr = 0; pr < LT_DK; ++pr) {
+        if (pr < nb) {  // grad(p_feat) = G_h + W_f[:, Z:]^T G_f; without z_feat_proj G_h's bits
+          float v[8];
+          unpack8(xh[pr], v);
+          if (p.nks_f) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const float f = e < 4 ? aP[pr][0][e & 3] : aP[pr][1][e & 3];
+              v[e] += ORDER == 0 ? f : lt_r16(f);
+            }
+          }
+          *(uint4*)(o + 2 * p.Z + pr * 32 + ch) = pack8(v);
+        }
+      }
+    }
+    t += (int)gridDim.x;
+    if (t >= p.ntiles) break;
+    request(t);
+  }
+}
+template <int ORDER>
+__global__ __launch_bounds__(256, 4) void latent_tail_det1_bwd_kernel(LtP p) {
+  CGEN_SETPRIO();
+  extern __shared__ __attribute__((aligned(16))) char lt_smem[];
+  lt_run_det1<ORDER>(p, lt_smem);
+}
+
+// The deterministic layer's wider instances (cgen_latent_tail_bwd without q_loc / q_ls): the two bodies above, nothing accumulated, the
+// sequential orders only (lt_reject declines the small-image shapes).  Instances of their own: the stochastic ones keep their code.
+template <int MAXKF, int ORDER>
+__global__ __launch_bounds__(256, 4) void latent_tail_det_bwd_kernel(LtP p) {
+  CGEN_SETPRIO();
+  extern __shared__ __attribute__((aligned(16))) char lt_smem[];
+  if (blockIdx.y == 0) lt_run_z<MAXKF, false, ORDER, true>(p, lt_smem);
+  else lt_run_p<MAXKF, false, ORDER>(p, lt_smem);
+}
+
 // ----------------------------------------------------------------------------- host
+static int lt_smallp_maxp() {
+  static const int v = [] { const char* e = getenv("CGEN_SMALLP_MAXP"); return e ? atoi(e) : 6000; }();
+  return v;
+}
+static bool lt_conv_knob_set() {  // a knob that changes which kernel cgen_conv2d serves a 1x1 conv with
+  return getenv("CGEN_CONV_NO_PX") || getenv("CGEN_CONV_NO_SMALLP") || getenv("CGEN_CONV_GENERIC") || getenv("CGEN_PX_MODE") ||
+         getenv("CGEN_SMALLP_MAXP_LONGK") || getenv("CGEN_SMALLP_LONGK");
+}
+static bool lt_is_det(const cgen_latent_tail_bwd_args* a) { return !a->q_loc.p && !a->q_ls.p; }
+
+// the deterministic form: out_p alone is written; only the conv_px order is built
+static const char* lt_reject_det(const cgen_latent_tail_bwd_args* a) {
+  if (a->gz_in.p || a->p_loc.p || a->p_ls.p || a->z.p || a->out_q.p) return "a reparam view without q_loc / q_ls";
+  if (a->acc_p || a->acc_q) return "the deterministic tail does not accumulate";
+  if ((int64_t)a->n * a->h * a->w <= lt_smallp_maxp() || a->h < 5 || a->w < 5) return "a shape of the small-image conv";
+  if (lt_conv_knob_set()) return "a conv dispatch knob is set";
+  return nullptr;
+}
+
 static const char* lt_reject(const cgen_latent_tail_bwd_args* a) {
   if (!a) return "null args";
   if (a->dtype != CGEN_F16) return "binary16 only";
   if (a->n < 1 || a->h < 1 || a->w < 1) return "empty problem";
   const int Z = a->z_dim, C = a->c;
+  const bool det = lt_is_det(a);
+  if (det) {
+    if (const char* why = lt_reject_det(a)) return why;
+  }
   if (Z != 8 && Z != 16) return "z_dim must be 8 or 16";
   if (C < 32 || C % 32 != 0 || C > 32 * LT_MAXKF) return "C must be a multiple of 32, at most 192";
   const int Cf = a->g_f.p ? a->g_f.c : 0;
@@ -311,8 +477,8 @@ static const char* lt_reject(const cgen_latent_tail_bwd_args* a) {
   const int64_t P = (int64_t)a->n * a->h * a->w;
   if (P >= (1ll << 31) / 2) return "too many pixels";
   struct { const cgen_view* v; int c; bool need; } vs[] = {
-      {&a->g_h, C, true},     {&a->g_f, Cf, false},  {&a->gz_in, Z, false}, {&a->q_loc, Z, true},         {&a->q_ls, Z, true},
-      {&a->p_loc, Z, true},   {&a->p_ls, Z, true},   {&a->z, Z, true},      {&a->out_p, 2 * Z + C, true}, {&a->out_q, 2 * Z, true}};
+      {&a->g_h, C, true},     {&a->g_f, Cf, false},  {&a->gz_in, Z, false}, {&a->q_loc, Z, !det},         {&a->q_ls, Z, !det},
+      {&a->p_loc, Z, !det},   {&a->p_ls, Z, !det},   {&a->z, Z, !det},      {&a->out_p, 2 * Z + C, true}, {&a->out_q, 2 * Z, !det}};
   for (auto& e : vs) {
     const cgen_view& v = *e.v;
     if (!v.p) {
@@ -327,6 +493,7 @@ static const char* lt_reject(const cgen_latent_tail_bwd_args* a) {
   }
   if (!a->img_pz || (a->g_f.p && (!a->img_fz || !a->img_fp))) return "a weight image is absent";
   if (((uintptr_t)a->img_pz | (uintptr_t)a->img_fz | (uintptr_t)a->img_fp) % 16) return "a weight image is not 16-byte aligned";
+  if (det) return nullptr;
   if (!a->coef) return "kl coefficient absent";
   if (a->coef_stride < 0) return "negative coef_stride";
   return nullptr;
@@ -361,7 +528,7 @@ extern "C" int cgen_latent_tail_bwd(const cgen_latent_tail_bwd_args* a, cgen_str
   const int parts = 1 + (p.C / 32 + LT_NP - 1) / LT_NP;
   // parity: the order the four launches sum in at this shape -- cgen_conv2d hands a 1x1 conv over few pixels (or a side below 5
   // that the caller cannot present as rows of 16 pixels) to conv_smallp_kernel, everything else here to conv_px_kernel
-  static const int smallp_maxp = [] { const char* e = getenv("CGEN_SMALLP_MAXP"); return e ? atoi(e) : 6000; }();
+  const int smallp_maxp = lt_smallp_maxp();
   const bool by_side = (a->h < 5 || a->w < 5) && (p.P % 16 != 0 || p.P < 256);
   const int order = !a->parity ? 0 : (p.P <= smallp_maxp || by_side) ? 2 : 1;
   // persistent over pixel tiles: as many workgroups as are resident at once (256 CUs), every part the same share
@@ -370,6 +537,21 @@ extern "C" int cgen_latent_tail_bwd(const cgen_latent_tail_bwd_args* a, cgen_str
   const int rounds = (p.ntiles + resident - 1) / resident;
   const int gx = (p.ntiles + rounds - 1) / rounds;  // every workgroup the same number of tiles: no half-empty last round
   const dim3 grid(gx, parts), block(256);
+  if (lt_is_det(a)) {  // (lt_reject: order is 0 or 1, nothing accumulates)
+    if (p.nks_f <= LT_DK && p.nks_h <= LT_DK) {  // one workgroup row: four workgroups per CU, every one the same number of tiles
+      const size_t lds1 = (size_t)32 * (kz + 8) * 2 + (size_t)p.nks_h * 32 * (kf + 8) * 2;
+      const int rounds1 = (p.ntiles + 1023) / 1024;
+      const dim3 grid1((p.ntiles + rounds1 - 1) / rounds1);
+      if (order == 0) hipLaunchKernelGGL((latent_tail_det1_bwd_kernel<0>), grid1, block, lds1, (hipStream_t)stream, p);
+      else hipLaunchKernelGGL((latent_tail_det1_bwd_kernel<1>), grid1, block, lds1, (hipStream_t)stream, p);
+      return check_launch("cgen_latent_tail_bwd(det)");
+    }
+#define LT_DET(KF_) do { if (order == 0) hipLaunchKernelGGL((latent_tail_det_bwd_kernel<KF_, 0>), grid, block, lds, (hipStream_t)stream, p); \
+                         else hipLaunchKernelGGL((latent_tail_det_bwd_kernel<KF_, 1>), grid, block, lds, (hipStream_t)stream, p); } while (0)
+    if (small) LT_DET(4); else LT_DET(LT_MAXKF);
+#undef LT_DET
+    return check_launch("cgen_latent_tail_bwd(det)");
+  }
 #define LT_LAUNCH(KF_, ACC_, ORD_) hipLaunchKernelGGL((latent_tail_bwd_kernel<KF_, ACC_, ORD_>), grid, block, lds, (hipStream_t)stream, p)
 #define LT_ORDER(KF_, ACC_) do { if (order == 0) LT_LAUNCH(KF_, ACC_, 0); else if (order == 1) LT_LAUNCH(KF_, ACC_, 1); else LT_LAUNCH(KF_, ACC_, 2); } while (0)
   if (small) { if (accum) LT_ORDER(4, true); else LT_ORDER(4, false); }
@@ -415,7 +597,10 @@ struct LfP {
 };
 
 // ROLE_P: this workgroup row computes h' (z_proj), else zf (z_feat_proj).  `part`: its index among the rows of its role.
-template <int ZD, int MAXK, int ORDER, bool ROLE_P>
+// DET: the layer is deterministic (z = p_loc, a channel slice of the prior Block's output): the z lanes of K-step 0 are 16-byte global
+// loads like every other operand lane, and everything tied to the KL chunk is absent -- no reparam, no z tile in LDS, no z store, no KL
+// partial, no barrier per tile.  (A tile keeps the chunk's LAT_CHUNK / Z pixels of one sample: pa is addressed per sample.)
+template <int ZD, int MAXK, int ORDER, bool ROLE_P, bool DET = false>
 __device__ __forceinline__ void lf_run(const LfP& p, char* smem, const int part) {
   constexpr int TP = LAT_CHUNK / ZD;  // pixels per tile
   constexpr int NF = TP / 64;         // 16-pixel fragments per wave and tile: 2 (Z = 16) or 4 (Z = 8), taken two at a time
@@ -433,9 +618,11 @@ __device__ __forceinline__ void lf_run(const LfP& p, char* smem, const int part)
   const bool first = ROLE_P && part == 0;  // the row that owns z and the KL partial
   float* sm = (float*)smem;
   char* zt = smem + 16;
-  char* wsl = zt + TP * ZLD * 2;
+  char* wsl = DET ? smem : zt + TP * ZLD * 2;
   uint64_t seed = 0, off = 0;
-  if (!p.eps) { seed = p.rng[0]; off = p.rng[1]; }
+  if constexpr (!DET) {
+    if (!p.eps) { seed = p.rng[0]; off = p.rng[1]; }
+  }
 
   uint4 ql, qs, pl, ps, ev, xb[2][MAXK], eh[ROLE_P ? 2 : 1][LF_NP], ep[ROLE_P ? 2 : 1][LF_NP];
   int b = 0, chunk = 0, e0 = 0, gpx = 0, xb_b = 0, xb_chunk = 0, opx[2];
@@ -466,7 +653,11 @@ __device__ __forceinline__ void lf_run(const LfP& p, char* smem, const int part)
         if (i < nks) {  // (uniform)
           const int c = i * 32 + fg * 8 - ZD;
           const bool s1 = c >= 0 && c < s1c;
-          if constexpr (ROLE_P) xb[f][i] = lt_ld(p.pa, xb_b * p.pa_sn + pc * p.pa_sw + c, s1);
+          if constexpr (DET) {  // (one load from a selected address: the lanes whose part of K-step 0 is z read p_loc)
+            const bool zl = i == 0 && c < 0;
+            const h16_t* s1p = ROLE_P ? p.pa + (xb_b * p.pa_sn + pc * p.pa_sw + c) : p.p_feat + (opx[f] * p.s_pf + c);
+            xb[f][i] = lt_ld(zl ? p.p_loc + (opx[f] * p.s_pl + fg * 8) : s1p, 0, zl || s1);
+          } else if constexpr (ROLE_P) xb[f][i] = lt_ld(p.pa, xb_b * p.pa_sn + pc * p.pa_sw + c, s1);
           else xb[f][i] = lt_ld(p.p_feat, opx[f] * p.s_pf + c, s1);
         }
       }
@@ -481,7 +672,8 @@ __device__ __forceinline__ void lf_run(const LfP& p, char* smem, const int part)
     }
   };
   int t = (int)blockIdx.x;
-  request_z(t);
+  if constexpr (DET) { b = t / p.chunks; chunk = t - b * p.chunks; }
+  else request_z(t);
   xb_b = b; xb_chunk = chunk;
   request_x(0);
   // ---- weight slab, once: LDS row pr * 32 + h * 16 + j holds output channel co_base + pr * 32 + (j >> 2) * 8 + h * 4 + (j & 3): MFMA h of
@@ -504,9 +696,10 @@ __device__ __forceinline__ void lf_run(const LfP& p, char* smem, const int part)
       binit[pr][h] = (f32x4_t){bb.x, bb.y, bb.z, bb.w};
     }
   const char* a_base = wsl + (fr * ldw + fg * 8) * 2;
+  if constexpr (DET) __syncthreads();  // the slab is visible (the stochastic form's first tile barrier does this)
   for (;;) {
     // ---- reparameterise: z to memory (row 0) and to the LDS tile, the KL partial of the chunk (row 0)
-    {
+    if constexpr (!DET) {
       float fql[8], fqs[8], fpl[8], fps[8], fe[8], fz[8];
       unpack8(ql, fql); unpack8(qs, fqs); unpack8(pl, fpl); unpack8(ps, fps);
       if (p.eps) unpack8(ev, fe);
@@ -526,11 +719,12 @@ __device__ __forceinline__ void lf_run(const LfP& p, char* smem, const int part)
     // the next tile's reparam operands are requested now: they arrive under this tile's MFMAs and stores
     t += (int)gridDim.x;
     const bool more = t < p.ntiles;
-    if (more) request_z(t);
+    if constexpr (DET) { b = t / p.chunks; chunk = t - b * p.chunks; }
+    else if (more) request_z(t);
 #pragma unroll
     for (int g = 0; g < NF / 2; ++g) {
       if (g > 0) request_x(g);
-      if (fg < CG) {  // this lane's part of K-step 0 is z
+      if (!DET && fg < CG) {  // this lane's part of K-step 0 is z
 #pragma unroll
         for (int f = 0; f < 2; ++f) xb[f][0] = *(const uint4*)(zt + (((wave * NF + g * 2 + f) * 16 + fr) * ZLD + fg * 8) * 2);
       }
@@ -610,7 +804,7 @@ __device__ __forceinline__ void lf_run(const LfP& p, char* smem, const int part)
         }
     }
     if (!more) break;
-    __syncthreads();  // every wave is done reading the z tile before the next one overwrites it
+    if constexpr (!DET) __syncthreads();  // every wave is done reading the z tile before the next one overwrites it
     xb_b = b; xb_chunk = chunk;
     request_x(0);
   }
@@ -629,11 +823,18 @@ __global__ __launch_bounds__(256, ORDER == 1 ? 3 : 2) void latent_tail_fwd_kerne
   else lf_run<ZD, MAXKF, ORDER, false>(p, lf_smem, (int)blockIdx.y - p.parts_p);
 }
 
-static inline int lf_pad(int v, int m) { return (v + m - 1) / m * m; }
-static int lf_smallp_maxp() {
-  static const int v = [] { const char* e = getenv("CGEN_SMALLP_MAXP"); return e ? atoi(e) : 6000; }();
-  return v;
+// The deterministic layer's instances (cgen_latent_tail_fwd without q_loc / q_ls): conv_px's order only (lf_reject declines the
+// small-image shapes).  Instances of their own: the stochastic ones keep their code.
+template <int ZD, int MAXKF>
+__global__ __launch_bounds__(256, 3) void latent_tail_det_fwd_kernel(LfP p) {
+  CGEN_SETPRIO();
+  extern __shared__ __attribute__((aligned(16))) char lf_smem[];
+  if ((int)blockIdx.y < p.parts_p) lf_run<ZD, LF_MAXKP, 1, true, true>(p, lf_smem, (int)blockIdx.y);
+  else lf_run<ZD, MAXKF, 1, false, true>(p, lf_smem, (int)blockIdx.y - p.parts_p);
 }
+
+static inline int lf_pad(int v, int m) { return (v + m - 1) / m * m; }
+static bool lf_is_det(const cgen_latent_tail_fwd_args* a) { return !a->q_loc.p && !a->q_ls.p; }
 
 static const char* lf_reject(const cgen_latent_tail_fwd_args* a) {
   if (!a) return "null args";
@@ -649,13 +850,16 @@ static const char* lf_reject(const cgen_latent_tail_fwd_args* a) {
   const int64_t P = (int64_t)a->n * a->h * a->w;
   if (P >= (1ll << 31) / 2) return "too many pixels";
   // which kernel cgen_conv2d serves the two convs with must be the same for both and known from the shape alone
-  if ((a->h < 5 || a->w < 5) && P > lf_smallp_maxp()) return "an image side below 5 with more pixels than the small-image conv takes";
-  if (getenv("CGEN_CONV_NO_PX") || getenv("CGEN_CONV_NO_SMALLP") || getenv("CGEN_CONV_GENERIC") || getenv("CGEN_PX_MODE") ||
-      getenv("CGEN_SMALLP_MAXP_LONGK") || getenv("CGEN_SMALLP_LONGK"))
-    return "a conv dispatch knob is set";
+  if ((a->h < 5 || a->w < 5) && P > lt_smallp_maxp()) return "an image side below 5 with more pixels than the small-image conv takes";
+  if (lt_conv_knob_set()) return "a conv dispatch knob is set";
+  const bool det = lf_is_det(a);  // z = p_loc: only h_out and zf are written; only the conv_px order is built
+  if (det) {
+    if (a->p_ls.p || a->eps.p || a->z.p) return "a reparam view without q_loc / q_ls";
+    if (P <= lt_smallp_maxp() || a->h < 5 || a->w < 5) return "a shape of the small-image conv";
+  }
   struct { const cgen_view* v; int c; bool need; } vs[] = {
-      {&a->q_loc, Z, true}, {&a->q_ls, Z, true}, {&a->p_loc, Z, true}, {&a->p_ls, Z, true}, {&a->p_feat, C, true}, {&a->h_in, C, true},
-      {&a->eps, Z, false},  {&a->z, Z, true},    {&a->h_out, C, true}, {&a->zf, Cf, false}};
+      {&a->q_loc, Z, !det}, {&a->q_ls, Z, !det}, {&a->p_loc, Z, true}, {&a->p_ls, Z, !det}, {&a->p_feat, C, true}, {&a->h_in, C, true},
+      {&a->eps, Z, false},  {&a->z, Z, !det},    {&a->h_out, C, true}, {&a->zf, Cf, false}};
   for (auto& e : vs) {
     const cgen_view& v = *e.v;
     if (!v.p) {
@@ -680,6 +884,7 @@ static const char* lf_reject(const cgen_latent_tail_fwd_args* a) {
   }
   if (!a->img_p || (a->zf.p && !a->img_f)) return "a weight image is absent";
   if (((uintptr_t)a->img_p | (uintptr_t)a->img_f | (uintptr_t)a->bias_p | (uintptr_t)a->bias_f) % 16) return "a weight image or bias is not 16-byte aligned";
+  if (det) return nullptr;
   if (!a->eps.p && !a->rng) return "neither eps nor rng";
   if (!a->kl_part || a->kl_stride < ceil_div((int64_t)a->h * a->w * Z, LAT_CHUNK)) return "kl_part absent or kl_stride below the chunk count";
   return nullptr;
@@ -714,13 +919,21 @@ extern "C" int cgen_latent_tail_fwd(const cgen_latent_tail_fwd_args* a, cgen_str
   const size_t lds = 16 + (size_t)(LAT_CHUNK / Z) * (Z + 8) * 2 + (size_t)LF_NP * 32 * (kmax + 8) * 2;
   // the order cgen_conv2d sums in at this shape (launch_conv): conv_smallp_kernel takes few pixels and sides below 5 (which lf_reject
   // admits only with few pixels), conv_px_kernel every other 1x1 conv with a short K
-  const int order = (P <= lf_smallp_maxp() || a->h < 5 || a->w < 5) ? 2 : 1;
+  const int order = (P <= lt_smallp_maxp() || a->h < 5 || a->w < 5) ? 2 : 1;
   // persistent over tiles: as many workgroups as are resident at once (three or two per CU, 256 CUs), every one the same number of tiles
   const int resident = (order == 1 ? 768 : 512) / parts;  // (parts <= 6)
   const int rounds = (p.ntiles + resident - 1) / resident;
   const int gx = (p.ntiles + rounds - 1) / rounds;
   const dim3 grid(gx, parts), block(256);
   const bool small = p.nks_f <= 5;
+  if (lf_is_det(a)) {  // (lf_reject: order is 1; LDS holds the slab alone)
+    const size_t lds_det = (size_t)LF_NP * 32 * (kmax + 8) * 2;
+#define LF_DET(Z_, KF_) hipLaunchKernelGGL((latent_tail_det_fwd_kernel<Z_, KF_>), grid, block, lds_det, (hipStream_t)stream, p)
+    if (Z == 16) { if (small) LF_DET(16, 5); else LF_DET(16, LF_MAXKF); }
+    else { if (small) LF_DET(8, 5); else LF_DET(8, LF_MAXKF); }
+#undef LF_DET
+    return check_launch("cgen_latent_tail_fwd(det)");
+  }
 #define LF_LAUNCH(Z_, KF_, ORD_) hipLaunchKernelGGL((latent_tail_fwd_kernel<Z_, KF_, ORD_>), grid, block, lds, (hipStream_t)stream, p)
 #define LF_ORDER(Z_, KF_) do { if (order == 1) LF_LAUNCH(Z_, KF_, 1); else LF_LAUNCH(Z_, KF_, 2); } while (0)
   if (Z == 16) { if (small) LF_ORDER(16, 5); else LF_ORDER(16, LF_MAXKF); }

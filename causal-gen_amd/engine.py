@@ -342,6 +342,12 @@ class Engine(WgradMixin):
         self.lat_tail_fwd = os.environ.get("CGEN_LAT_TAIL_FWD", "1") != "0"
         self.lat_tail_fwd_minpx = int(os.environ.get("CGEN_LAT_TAIL_FWD_MINPX", "0"))  # layers with fewer pixels (n * h * w) keep the three launches
         self.lat_tails_fwd = 0  # fused forward launches since begin()
+        # The DETERMINISTIC decoder layers (z = p_loc: the layers above z_max_res, the largest tensors of the model) the same way, both
+        # directions (the same two entry points without q_loc / q_ls; latent_tail_det_fwd / _bw_latent_tail_det).  0: z_proj and
+        # z_feat_proj as launches of their own, their data gradients, the residual's copy into grad(p_feat) and the zero fill of grad(p_ls).
+        self.lat_tail_det = os.environ.get("CGEN_LAT_TAIL_DET", "1") != "0"
+        self.lat_tails_det = 0      # fused launches of deterministic layers in the last backward()
+        self.lat_tails_det_fwd = 0  # ... in forward passes since begin()
         # The discretised-Gaussian likelihood head of a recorded pass -- the 1x1 convs x_loc / x_logscale and the NLL around them -- as
         # one launch each way (cgen_dgauss_head_fwd / _bwd; like_head_fwd / _bw_like_head below): the bits of the three forward and
         # the six backward launches it stands for, ONE tape entry.  0: those launches.
@@ -450,7 +456,7 @@ class Engine(WgradMixin):
         self._wg_forked = False
         self._split_done = False
         self.passes = 0
-        self.lat_tails_fwd = 0
+        self.lat_tails_fwd = self.lat_tails_det_fwd = 0
         self.like_heads = 0
         self.stream = torch.cuda.current_stream(self.device).cuda_stream
 
@@ -1300,6 +1306,46 @@ class Engine(WgradMixin):
                 (self.tape if tape_hold is None else tape_hold).append((self._bw_conv, (site_f, [z, p_feat], ACT_NONE, zf, None, None), 0))
         return z, h2, zf
 
+    def latent_tail_det_fwd(self, site_p, site_f, p_loc, p_feat, h, pa, tape_hold=None):
+        """A deterministic layer's tail (z = p_loc): conv(z_proj, [p_loc, pa], res1=h, res2=p_feat, trunk=True) -> conv(z_feat_proj,
+        [p_loc, p_feat]) (`site_f` None: the layer has none) as ONE launch on the current stream, with the two launches' bits and their
+        two tape entries in their places (z_feat_proj's goes to `tape_hold`).  Returns (h', zf or None), or None -- nothing done, the
+        caller runs the two launches -- under the conditions of latent_tail_fwd."""
+        if not self.lat_tail_det or self.dt != F16 or self.prof is not None or self._ablate:
+            return None
+        n, hh, ww, zd, c = p_loc.n, p_loc.h, p_loc.w, p_loc.c, site_p.co
+        if h.rem or p_feat.rem or (self.trunk_rem and max(hh, ww) <= self.trunk_maxres):
+            return None
+        if site_p.ks != 1 or list(site_p.seg_c) != [zd, pa.c] or (site_f is not None and (site_f.ks != 1 or list(site_f.seg_c) != [zd, c])):
+            return None
+        t = _lib.LatentTailFwdArgs()
+        t.dtype, t.n, t.h, t.w, t.z_dim, t.c, t.ctx = self.dt, n, hh, ww, zd, c, pa.c
+        t.p_loc, t.p_feat, t.h_in, t.pa = p_loc.cv(), p_feat.cv(), h.cv(), pa.cv()
+        t.q_loc = t.q_ls = t.p_ls = t.eps = t.z = NULL_VIEW  # (absent q_loc / q_ls: the deterministic form)
+        probe = lambda c_: View(h.base.ptr, hh * ww * c_, ww * c_, c_, c_, 0)  # (see latent_tail_fwd)
+        t.h_out, t.zf = probe(c), (NULL_VIEW if site_f is None else probe(site_f.co))
+        t.img_p, t.img_f = site_p.img_fwd, (site_f.img_fwd if site_f is not None else None)
+        bp, bf = site_p.conv.bias, (site_f.conv.bias if site_f is not None else None)
+        t.bias_p, t.bias_f = (bp.data_ptr() if bp is not None else None), (bf.data_ptr() if bf is not None else None)
+        if not self.lib.latent_tail_fwd_supported(C.byref(t)):
+            return None
+        # ---- committed: the allocations, the launches' bookkeeping and the tape entries of the two calls, in their order
+        h2 = self.new(n, hh, ww, c)
+        zf = self.new(n, hh, ww, site_f.co) if site_f is not None else None
+        t.h_out, t.zf = h2.cv(), (zf.cv() if zf is not None else NULL_VIEW)
+        self.lib.latent_tail_fwd(C.byref(t), self.stream)
+        self.launches += 1
+        self.lat_tails_det_fwd += 1
+        if self.recording:
+            if self._dbg_names is not None:
+                self._dbg_names[id(h2.base)] = site_p.name
+            self.tape.append((self._bw_conv, (site_p, [p_loc, pa], ACT_NONE, h2, h, p_feat), self._bw_tag))
+            if zf is not None:
+                if self._dbg_names is not None:
+                    self._dbg_names[id(zf.base)] = site_f.name
+                (self.tape if tape_hold is None else tape_hold).append((self._bw_conv, (site_f, [p_loc, p_feat], ACT_NONE, zf, None, None), self._bw_tag))
+        return h2, zf
+
     def _like_head_args(self, site_loc, site_ls, h, params, x):
         t = _lib.DgaussHeadArgs()
         t.dtype, t.n, t.h, t.w = self.dt, h.n, h.h, h.w
@@ -1702,7 +1748,7 @@ class Engine(WgradMixin):
         main_t = torch.cuda.current_stream(self.device)
         if self._side_join_pending:  # side-stream work of the forward pass nobody has joined yet (the stem's im2col)
             self.join_side()
-        self.blk3_pairs = self.conv_pairs = self.blk4_pairs = self.lat_tails = 0
+        self.blk3_pairs = self.conv_pairs = self.blk4_pairs = self.lat_tails = self.lat_tails_det = 0
         skip = 0
         tape = self.tape
         for i in range(len(tape) - 1, -1, -1):
@@ -1728,7 +1774,7 @@ class Engine(WgradMixin):
                 if self.lat_tail and fn == self._bw_conv and self.dt == F16 and self.prof is None:
                     ents = self._latent_tail_at(i)
                     if ents is not None and self._bw_latent_tail(*ents):
-                        skip = (2 if ents[0] is not None else 1)
+                        skip = sum(e is not None for e in ents) - 1  # (the entries behind tape[i] the launch has absorbed)
                         continue
                 if self.conv_pair and fn == self._bw_conv and self.dt != F32 and self._two_unfused_blocks(i):
                     # X.conv2 | Y.conv2 in one launch, then X.conv1, Y.conv1 (their own gradient outputs pair inside _bw_conv)
@@ -1849,7 +1895,7 @@ class Engine(WgradMixin):
             if a is None or f[1][0] is not a[1][0] or not (f[1][1].rg and f[0].seg_rg[1]):
                 return None
         if i < 1 or tape[i - 1][0] != self._bw_reparam:
-            return None
+            return self._latent_tail_det(f, a)
         r = tape[i - 1][1]
         q_loc, q_ls, p_loc, p_ls, z = r[:5]
         site, segs, _, out, r1, r2 = a
@@ -1867,9 +1913,77 @@ class Engine(WgradMixin):
             return None
         return f, a, r
 
+    def _latent_tail_det(self, f, a):
+        """The deterministic form of the pattern (no reparam entry in front; z = p_loc): z_proj's first segment is the channel slice
+        [0, Z) of the base -- the prior Block's output -- whose slice [2Z, 2Z + C) is its residual, z_feat_proj (if any) reads the same
+        two slices.  Returns (f, a, None), else None."""
+        if not self.lat_tail_det:
+            return None
+        site, segs, _, out, r1, r2 = a
+        z = segs[0]
+        pb, zd = z.base, z.c
+        if z is pb or z.coff != 0 or pb.c != 2 * zd + site.co or (segs[1].rg and site.seg_rg[1]):
+            return None
+        pf = [t for t in (r1, r2) if t is not None and t.base is pb]  # the residual that is p_feat
+        if len(pf) != 1 or not pf[0].rg or pf[0].coff != 2 * zd or pf[0].c != site.co:
+            return None
+        if f is not None and (f[1][1].base is not pb or f[1][1].coff != 2 * zd or f[1][1].c != site.co):
+            return None
+        return f, a, None
+
+    def _bw_latent_tail_det(self, f, a):
+        """The one or two entries _latent_tail_det found as one cgen_latent_tail_bwd launch (its form without q_loc / q_ls): the data
+        gradients into grad(p_loc), grad(p_feat) with the residual's share, and zeros for grad(p_ls), which nobody writes -- the whole
+        2Z + C pixel of the prior Block's output gradient, so no copy is parked as a rider and no fill follows.  Returns False --
+        nothing done -- as _bw_latent_tail does, and when that gradient already holds a value (the kernel does not accumulate)."""
+        site_z, segs_z, _, out_z, r1, r2 = a
+        p_loc = segs_z[0]
+        zd, c = p_loc.c, site_z.co
+        if self._ablate:
+            return False
+        pall = p_loc.base.chan(0, 2 * zd + c)
+        e = self.grads.get(id(p_loc.base))
+        if e is not None and self._missing(e[1], 0, 2 * zd + c) != [(0, 2 * zd + c)]:
+            return False
+        if self._frozen(pall) or id(p_loc.base) in self._riders:
+            return False
+        g_h = self.grad_read(out_z)
+        if g_h is None:
+            return False
+        g_f = self.grad_read(f[3]) if f is not None else None
+        t = _lib.LatentTailArgs()
+        t.dtype, t.n, t.h, t.w, t.z_dim, t.c = self.dt, p_loc.n, p_loc.h, p_loc.w, zd, c
+        t.parity = 0 if self.lat_tail_exact else 1
+        t.g_h = g_h.cv()
+        t.g_f = g_f.cv() if g_f is not None else NULL_VIEW
+        t.gz_in = t.q_loc = t.q_ls = t.p_loc = t.p_ls = t.z = t.out_q = NULL_VIEW  # (absent q_loc / q_ls: the deterministic form)
+        t.out_p = self._gentry(p_loc.base)[0].chan(0, 2 * zd + c).cv()  # (the view grad_write will hand out below)
+        if g_f is not None:
+            t.img_fz, t.img_fp = f[0].img_dg[0], f[0].img_dg[1]
+        t.img_pz = site_z.img_dg[0]
+        if not self.lib.latent_tail_bwd_supported(C.byref(t)):
+            return False
+        # ---- committed: the bookkeeping of the entries, in their order
+        if g_f is not None and self._needs_wgrad(f[0]):
+            self._wgrad(f[0], f[1], ACT_NONE, g_f)
+        for res in (r1, r2):
+            if res is not None and res.rg and res.base is not p_loc.base:  # (p_feat's share of G_h is added by the kernel)
+                self._grad_residual(res, g_h, out_z, segs_z)
+        if self._needs_wgrad(site_z):
+            self._wgrad(site_z, segs_z, ACT_NONE, g_h)
+        gp, acc_p = self.grad_write(pall)
+        assert not acc_p
+        t.out_p = gp.cv()
+        self.lib.latent_tail_bwd(C.byref(t), self.stream)
+        self.launches += 1
+        self.lat_tails_det += 1
+        return True
+
     def _bw_latent_tail(self, f, a, r):
         """The three entries _latent_tail_at found as one cgen_latent_tail_bwd launch.  Returns False -- nothing done, the caller runs
         the four launches -- when the kernel does not serve the shapes or a gradient buffer involved may not be written in place."""
+        if r is None:
+            return self._bw_latent_tail_det(f, a)
         q_loc, q_ls, p_loc, p_ls, z, logt, fb_col, coef_ptr = r
         site_z, segs_z, _, out_z, r1, r2 = a
         zd, c = z.c, site_z.co

@@ -787,6 +787,17 @@ class HVAE(nn.Module):
                             out.append((p_loc, p_ls))
             else:
                 z = p_loc
+                # z_proj and z_feat_proj as ONE launch where the kernel serves the layer: the same bits, the same two tape entries
+                # (z_feat_proj's in `hold`); no fork is pending here (`two` needs a stochastic layer).  Training and abduction passes, as above.
+                dtail = eng.latent_tail_det_fwd(self._site(eng, blk.z_proj), self._site(eng, blk.z_feat_proj) if feat else None,
+                                                p_loc, p_feat, h, pa, tape_hold=hold) if acts is not None else None
+                if dtail is not None:
+                    t_zp = len(eng.tape)
+                    h = self._run_block(eng, blk.conv, [dtail[0]])
+                    if feat:
+                        z = dtail[1]
+                    eng.tape[t_zp:t_zp] = hold
+                    continue
             z_cur = z
             # the next layer's prior chain (z_feat_proj -> prior Block) on the side stream, forked HERE but enqueued behind z_proj:
             # the main chain must be the first edge out of the fork for a captured graph to keep it on one queue (Engine.fork_mark)

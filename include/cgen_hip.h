@@ -461,7 +461,12 @@ int cgen_mediator_mix(int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c,
  * (rows x (ceil32(g_f.c) + 32)), img_pz = the z segment of z_proj (rows x (ceil32(C) + 32)); img_fz / img_fp are not read without g_f.
  * Served (cgen_latent_tail_bwd_supported() == 1, answered without a GPU): CGEN_F16; Z in {8, 16}; C and g_f.c multiples of 32 up to
  * 192; every view 16-byte aligned, linear in pixels (sn == h * sh, sh == w * sw) and below 2^31 bytes.  Anything else:
- * _supported() == 0 and cgen_latent_tail_bwd returns CGEN_EUNSUPPORTED without launching. */
+ * _supported() == 0 and cgen_latent_tail_bwd returns CGEN_EUNSUPPORTED without launching.
+ * The DETERMINISTIC form (q_loc.p == NULL and q_ls.p == NULL; no struct change): the layer takes z = p_loc, so g_z IS grad(p_loc):
+ *   out_p = [g_z | 0 | g_pfeat]                                   (the p_ls channels are written as zeros; out_q does not exist)
+ * gz_in, p_loc, p_ls, z, out_q must be absent and acc_p / acc_q 0 (it does not accumulate); coef, chan_scale, logt are not read.
+ * Only the conv_px order is built (parity 1), so what cgen_conv2d serves with its small-image kernel is declined: n*h*w up to its
+ * pixel limit (6000), an image side below 5, or a conv dispatch knob in the environment. */
 typedef struct cgen_latent_tail_bwd_args {
   int32_t dtype, n, h, w, z_dim, c;
   int32_t coef_stride, acc_q, acc_p;
@@ -496,7 +501,11 @@ int cgen_latent_tail_bwd(const cgen_latent_tail_bwd_args* a, cgen_stream_t strea
  * Served (cgen_latent_tail_fwd_supported() == 1, answered without a GPU): CGEN_F16; Z in {8, 16}; C and zf.c multiples of 32 up to
  * 192; Z + ceil8(ctx) <= 64; no remainder planes (h_in_rem == h_out_rem == 0); every view 16-byte aligned, linear in pixels
  * (sn == h * sh, sh == w * sw; pa as above) and below 2^31 bytes; an image side below 5 only up to the small-image conv's pixel limit.
- * Anything else: _supported() == 0 and cgen_latent_tail_fwd returns CGEN_EUNSUPPORTED without launching. */
+ * Anything else: _supported() == 0 and cgen_latent_tail_fwd returns CGEN_EUNSUPPORTED without launching.
+ * The DETERMINISTIC form (q_loc.p == NULL and q_ls.p == NULL; no struct change): the layer takes z = p_loc --
+ *   h_out = rn16(bias_p + W_p [p_loc | pa] + h_in + p_feat)       zf = rn16(bias_f + W_f [p_loc | p_feat])
+ * with cgen_conv2d x 2's bits; nothing else is written.  p_ls, eps and z must be absent; rng, kl_part, kl_stride, stream_id and logt are
+ * not read.  Only the conv_px order is built: n*h*w up to the small-image conv's pixel limit (6000) or an image side below 5 is declined. */
 typedef struct cgen_latent_tail_fwd_args {
   int32_t dtype, n, h, w, z_dim, c;     /* c: channels of h_in, h_out and p_feat */
   int32_t ctx;                          /* channels of pa */

@@ -5,6 +5,9 @@ Same step selection as tools/timeline.py (the shortest whole step = a graph repl
 The forward tails are reported as well: per layer the reparam_kl_fwd launch and the two 1x1 convs over [z | .] behind it (z_proj on
 the reparam's queue, z_feat_proj usually on the side queue) -- first start .. last end of the three, and the main-chain part alone
 (reparam start .. z_proj end); in the fused path one latent_tail_fwd_kernel.
+Last, the DETERMINISTIC layers at the top resolution (no reparam launch marks them): every launch between the last upsample and the
+likelihood head, and between elbo_finalize and the first upsample_bwd, that is neither a Block nor the head -- the 1x1 convs, their
+data gradients, the landed rider and the zero fill, or latent_tail_det_fwd_kernel / latent_tail_det_bwd_kernel.
 usage: python tools/lat_tail_timeline.py <kernel_trace.csv> [out.txt]"""
 import collections
 import csv
@@ -109,6 +112,25 @@ for sig, (durs, spans, mains) in fgroups.items():
         P("        %9s  %-44s %5d x %d" % ("%6.1f us" % m, name, gx, gy))
 P("sum of the forward tails' spans: %.3f ms, of their main-chain parts: %.3f ms, in %d layers; forward chain (step start .. elbo_finalize start) %.3f ms"
   % (ftotal / 1e3, fmain / 1e3, sum(len(v[0]) for v in fgroups.values()), (step[fin][0] - step[0][0]) / 1e6))
+
+# ---- the deterministic layers at the top resolution (z = p_loc: no reparam launch marks them): forward, what runs between the last
+# upsample and the likelihood head that is neither a Block nor the head; backward, the same between elbo_finalize and the first
+# upsample_bwd.  Separate launches: 1x1 convs over [p_loc | .] / their data gradients, the landed rider (axpby) and the zero fill of
+# grad(p_ls); fused: latent_tail_det_fwd_kernel / latent_tail_det_bwd_kernel.
+def det_rows(lo, hi):
+    skip = ("blk3", "blk4", "dgauss", "elbo_finalize", "upsample", "nll")
+    return [r for r in step[lo:hi] if not any(s in r[2] for s in skip)]
+
+
+ups_f = [k for k in range(fin) if "upsample_fwd" in step[k][2]]
+ups_b = [k for k in range(fin, len(step)) if "upsample_bwd" in step[k][2]]
+if ups_f and ups_b:
+    t0 = step[0][0]
+    for title, rows_ in (("forward", det_rows(ups_f[-1] + 1, fin)), ("backward", det_rows(fin + 1, ups_b[0]))):
+        P("deterministic top-resolution layers, %s: start us | us | kernel | workgroups x parts" % title)
+        for r in rows_:
+            P("    %9.1f | %6.1f | %-44s | %5d x %d" % ((r[0] - t0) / 1e3, (r[1] - r[0]) / 1e3, short(r[2]), r[3], r[4]))
+        P("  %d launches, sum %.1f us" % (len(rows_), sum(r[1] - r[0] for r in rows_) / 1e3))
 txt = "\n".join(out)
 print(txt)
 if len(sys.argv) > 2:
