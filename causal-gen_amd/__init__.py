@@ -5,7 +5,8 @@ model classes raise if the library or a GPU is missing."""
 __version__ = "0.1.0"
 
 
-_LAZY = {"DeviceDataset": "data", "DeviceLoader": "data", "PgmCounterfactual": "pgm_cf", "DevicePGM": "pgm_cf"}
+_LAZY = {"DeviceDataset": "data", "DeviceLoader": "data", "PgmCounterfactual": "pgm_cf", "DevicePGM": "pgm_cf",
+         "ChestPredictor": "predictor_resnet"}
 
 
 def __getattr__(name):  # the data pipeline's and the device PGM's classes, re-exported without importing torch at package import

@@ -103,6 +103,13 @@ class MlpTrainHead(C.Structure):
                 ("ggamma", C.c_void_p * 2), ("gbeta", C.c_void_p * 2)]
 
 
+class ResnetArgs(C.Structure):
+    """cgen_resnet_args: the weight images, GroupNorm parameters, heads and observations of ChestPredictor's one trunk."""
+    _fields_ = [("res", C.c_int32), ("ctx_stride", C.c_int32), ("std_fixed", C.c_float), ("obs_stride", C.c_int32 * 4),
+                ("reserved", C.c_int32), ("img_fwd", C.c_void_p * 20), ("img_dg", C.c_void_p * 20), ("gamma", C.c_void_p * 20),
+                ("beta", C.c_void_p * 20), ("fc_w", C.c_void_p * 4), ("fc_b", C.c_void_p * 4), ("obs", C.c_void_p * 4), ("ctx", C.c_void_p)]
+
+
 class AugmentArgs(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("c", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32), ("r_h", C.c_int32),
                 ("r_w", C.c_int32), ("pad_x", C.c_int32), ("pad_y", C.c_int32), ("ctx", C.c_int32), ("stream_id", C.c_uint32),
@@ -182,6 +189,7 @@ STREAM_AUGMENT = 980  # Philox stream id of cgen_batch_augment (the list of take
 PRED_NORMAL, PRED_CATEGORICAL, PRED_BERNOULLI = 0, 1, 2
 PRED_MAX_HEADS, PRED_MAX_OUT = 4, 16
 MLP_MAX_IN, MLP_MAX_WIDTH = 8, 64
+RESNET_CONVS, RESNET_SITES = 20, 18
 
 i32, i64, u32, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p
 
@@ -284,6 +292,10 @@ PROTOTYPES = {
     "cgen_mlp_train_workspace": [C.POINTER(MlpTrainHead), i32, C.POINTER(i64)],
     "cgen_mlp_train_fwd": [C.POINTER(MlpTrainHead), i32, vp, i64, f32, vp, vp, vp],
     "cgen_mlp_train_bwd": [C.POINTER(MlpTrainHead), i32, vp, i64, vp, vp],
+    "cgen_resnet_workspace": [i32, i32, C.POINTER(i64)],
+    "cgen_resnet_site": [i32, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)],
+    "cgen_resnet_fwd": [C.POINTER(ResnetArgs), i32, vp, vp, i64, vp, vp, vp, vp],
+    "cgen_resnet_bwd": [C.POINTER(ResnetArgs), i32, vp, i64, vp, vp, vp],
     "cgen_pgm_workspace": [C.POINTER(PgmMech), i32, i32, C.POINTER(i64)],
     "cgen_pgm_nll_fwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp],
     "cgen_pgm_nll_fwd_bwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp, vp, i64, vp],

@@ -9,7 +9,7 @@ effectiveness (do the anticausal predictors find the intervened value in the cou
 intervention move the image?) and reversibility (how far does an intervention followed by its undo move it?); the last two are
 image-side loops over ``dscm.counterfactual`` measured by ``cgen_image_dist``.  Every number is bit-identical from run to run.
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -76,6 +76,15 @@ def metric_specs(dataset: str, min_max: Optional[Dict[str, Sequence[float]]] = N
                 MetricSpec("age", "continuous", 1, "none", ("mae",), 50.0, 50.0, 50.0, 50.0, 1.0),
                 MetricSpec("race", "categorical", 3, "none", ("acc", "rocauc"))]
     raise ValueError(f"no metric table for dataset {dataset!r}")
+
+
+def chest_metric_specs(raw: bool = True) -> List[MetricSpec]:
+    """The mimic table of ``metric_specs`` with the transforms ``predictor_resnet.ChestPredictor``'s raw head outputs need:
+    sigmoid for sex and finding, softmax for race, none for age (its (v + 1) * 50 scaling stays) -- so that
+    ``MetricAccumulator(chest_metric_specs()).update_from(ChestPredictor, ...)`` works in place like the other data sets.
+    ``raw=False``: ``metric_specs("mimic")`` itself (for ``predict()``'s probabilities)."""
+    tr = {"sex": "sigmoid", "finding": "sigmoid", "race": "softmax", "age": "none"}
+    return [replace(s, transform=tr[s.name]) if raw else s for s in metric_specs("mimic")]
 
 
 def _rows(v: Tensor, n: Optional[int], device, what: str) -> Tensor:

@@ -465,6 +465,7 @@ def make_predictor(args) -> _AnticausalPredictor:
     if "cmnist" in ds:
         return ColourMNISTPredictor(args)
     if "mimic" in ds:
+        # (mimic's predictor exists -- predictor_resnet.ChestPredictor(args), constructed directly; this factory keeps its answer)
         raise NotImplementedError("ChestPGM's anticausal predictors (ResNet-18 heads) are not implemented on this backend")
     raise ValueError(f"no anticausal predictor for dataset {ds!r}")
 

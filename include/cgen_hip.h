@@ -733,6 +733,53 @@ int cgen_predictor_train_fwd(const cgen_pred_train_head* heads, int32_t nheads, 
 int cgen_predictor_train_bwd(const cgen_pred_train_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, int64_t ws_floats,
                              const float* coef_dev, float* dx, cgen_stream_t);
 
+/* ------------------------------------------------------------------ ChestPGM's anticausal heads (additive in ABI 411; csrc/predictor_resnet.inc)
+ * pgm/resnet.py ResNet18 with GroupNorm (flow_pgm.py:568-602, 659-703: encoder_s / encoder_r / encoder_f / encoder_a of the mimic
+ * PGM) in eval mode -- 7x7/s2 stem, GroupNorm, ReLU, MaxPool2d(3, 2, 1), four stages of two residual blocks (64 / 128 / 256 / 512
+ * channels; GroupNorm(min(32, c / 4), c), eps 1e-5; no conv bias; a 1x1/s2 conv + GroupNorm on the identity of the first block of
+ * stages 2-4), spatial mean -- run ONCE and followed by the four Linear heads (the reference runs four equal copies of the trunk)
+ * and the likelihoods of model_anticausal: Bernoulli(sigmoid) for sex and finding, OneHotCategorical(softmax) over 3 races,
+ * Normal(loc, softplus(logscale) or std_fixed) without tanh for age, whose Linear also sees `finding` (513 inputs).
+ * f32 NHWC.  x is [n, 1, res, res] f32 contiguous, 32 <= res <= 256, odd sizes included.  Heads, terms and outs are in the order
+ * sex, race, finding, age.  Convs, in the order of img_fwd / img_dg / gamma / beta: 0 = stem; 1 + 2k / 2 + 2k = conv1 / conv2 of
+ * block k = 0..7; 16 + s = the identity conv of stage s = 1..3.  The weight images are cgen_weight_prep's, CGEN_F32: mode 0
+ * (forward) and mode 1 (data gradient) of the OIHW parameter as it is for the stride-1 3x3 convs (ks 3) and the 1x1 convs (ks 1);
+ * the stem and conv1 of blocks 2, 4, 6 (stride 2) run on patch tensors (cgen_im2col_strided), so their parameter is imaged as the
+ * 1x1 conv [co][ci * ks * ks] that it is there.
+ * The forward keeps every raw conv output, every post-ReLU activation and the per-(image, group) mean and 1 / std in ws; the
+ * backward reads them (it does NOT recompute the forward) and may run any number of times after a forward with the same n and ws.
+ * Every launch goes on `stream`; no allocation, synchronisation or host read of device data (capturable).  All sums run in a fixed
+ * order without atomics: reruns are bit-identical, and image b's results do not depend on n or on b's position. */
+#define CGEN_RESNET_CONVS 20
+#define CGEN_RESNET_SITES 18
+typedef struct cgen_resnet_args {
+  int32_t res;
+  int32_t ctx_stride;                      /* row stride (floats) of ctx */
+  float std_fixed;                         /* age: > 0 = constant scale, else softplus(out[1]) */
+  int32_t obs_stride[4];                   /* row strides (floats) of obs */
+  int32_t reserved;
+  const void* img_fwd[CGEN_RESNET_CONVS];
+  const void* img_dg[CGEN_RESNET_CONVS];
+  const float* gamma[CGEN_RESNET_CONVS];   /* GroupNorm weight / bias, 16-byte aligned */
+  const float* beta[CGEN_RESNET_CONVS];
+  const float* fc_w[4];                    /* [1][512], [3][512], [1][512], [2][513] */
+  const float* fc_b[4];
+  const float* obs[4];                     /* sex [n][1], race [n][3] one-hot, finding [n][1], age [n][1]; read only with terms */
+  const float* ctx;                        /* finding, the age head's context column: ctx[b * ctx_stride] */
+} cgen_resnet_args;
+/* floats of workspace for n images of res x res */
+int cgen_resnet_workspace(int32_t n, int32_t res, int64_t* floats);
+/* Where a post-ReLU activation lives in ws after a forward: NHWC [n, h, h, c] at float offset `offset`.  site 0 = the stem,
+ * 1 + 2k / 2 + 2k = relu(bn1) / the output of block k, 17 = the max-pool's output. */
+int cgen_resnet_site(int32_t n, int32_t res, int32_t site, int64_t* offset, int32_t* h, int32_t* c);
+/* terms (optional) [n][4] = -log p_h(obs_h[b] | x[b]); outs (optional) [4][n][CGEN_PRED_MAX_OUT] = the raw head outputs; loss
+ * (optional, needs terms) = the sum of all terms in a fixed order. */
+int cgen_resnet_fwd(const cgen_resnet_args* a, int32_t n, const float* x, float* ws, int64_t ws_floats, float* terms, float* outs,
+                    float* loss, cgen_stream_t);
+/* dx [n, 1, res, res] = coef_dev[0] * d(sum of terms)/dx (overwritten) from the state the forward left in ws. */
+int cgen_resnet_bwd(const cgen_resnet_args* a, int32_t n, float* ws, int64_t ws_floats, const float* coef_dev, float* dx,
+                    cgen_stream_t);
+
 /* ------------------------------------------------------------------ scalar predictor head, TRAINING mode (additive in ABI 411; csrc/predictor_mlp.inc)
  * pgm/layers.py MLP in train mode (layers.py:46-59), scored as flow_pgm.py:260-267 scores encoder_a: q(a | b, v) = Normal(MLP(b, v)).
  *   mlp.0 Linear nin -> w (no bias), mlp.1 BatchNorm1d(w), LeakyReLU(0.01), mlp.3 Linear w -> w (no bias), mlp.4 BatchNorm1d(w),
