@@ -574,7 +574,10 @@ __device__ __forceinline__ float dm_logprob(float xv, float mean, float ls_raw, 
   }
   if (d_mean) {
     *d_mean = -(dup + dum + dmid) * inv;
-    *d_ls = (ls_raw > DM_MIN_LS) ? (-(dup * up + dum * um + dmid * mid) + dls_direct) : 0.f;
+    // the reference clamps with torch.max(t, -7 * ones) (dmol.py const_max): all of the gradient above the clamp, none below, and
+    // one half on a tie (-7 is exact in both storage formats, so a tie can occur)
+    const float pass = ls_raw > DM_MIN_LS ? 1.f : (ls_raw == DM_MIN_LS ? 0.5f : 0.f);
+    *d_ls = pass > 0.f ? pass * (-(dup * up + dum * um + dmid * mid) + dls_direct) : 0.f;
   }
   return lp;
 }

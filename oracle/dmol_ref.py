@@ -34,7 +34,7 @@ def dmol_nll(x, l, low_bit=False):
     """-log p(x) / (H*W*3) per sample (nats/dim), dmol.py:24-118; ``low_bit``: the 5-bit branch (dmol.py:52-60, 88-102)."""
     hb, scale = (1.0 / 31.0, 15.5) if low_bit else (1.0 / 255.0, 127.5)
     logits, means, ls, co = _unpack(l)
-    ls = torch.clamp(ls, min=MIN_LOG_SCALE)
+    ls = torch.max(ls, torch.ones_like(ls) * MIN_LOG_SCALE)  # const_max, dmol.py:14-16: binary max, so half the gradient on a tie
     co = torch.tanh(co)
     xe = x.unsqueeze(-1).expand(*x.shape, NMIX)  # [B,H,W,3,M]
     m_r = means[..., 0, :]
