@@ -110,6 +110,12 @@ class ResnetArgs(C.Structure):
                 ("beta", C.c_void_p * 20), ("fc_w", C.c_void_p * 4), ("fc_b", C.c_void_p * 4), ("obs", C.c_void_p * 4), ("ctx", C.c_void_p)]
 
 
+class ResnetTrainArgs(C.Structure):
+    """cgen_resnet_train_args: the eval record, every gradient destination, Dropout's probability and Philox state."""
+    _fields_ = [("net", ResnetArgs), ("gw", C.c_void_p * 20), ("ggamma", C.c_void_p * 20), ("gbeta", C.c_void_p * 20),
+                ("gfc_w", C.c_void_p * 4), ("gfc_b", C.c_void_p * 4), ("rng", C.c_void_p), ("p_dropout", C.c_float), ("reserved", C.c_int32)]
+
+
 class AugmentArgs(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("c", C.c_int32), ("h0", C.c_int32), ("w0", C.c_int32), ("r_h", C.c_int32),
                 ("r_w", C.c_int32), ("pad_x", C.c_int32), ("pad_y", C.c_int32), ("ctx", C.c_int32), ("stream_id", C.c_uint32),
@@ -296,6 +302,10 @@ PROTOTYPES = {
     "cgen_resnet_site": [i32, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)],
     "cgen_resnet_fwd": [C.POINTER(ResnetArgs), i32, vp, vp, i64, vp, vp, vp, vp],
     "cgen_resnet_bwd": [C.POINTER(ResnetArgs), i32, vp, i64, vp, vp, vp],
+    "cgen_resnet_train_workspace": [i32, i32, C.POINTER(i64)],
+    "cgen_resnet_train_fwd": [C.POINTER(ResnetTrainArgs), i32, vp, vp, i64, vp, vp, vp, vp],
+    "cgen_resnet_train_bwd": [C.POINTER(ResnetTrainArgs), i32, vp, vp, i64, vp, vp, vp],
+    "cgen_resnet_dropout_keep": [vp, f32, i32, i32, i32, vp, vp],
     "cgen_pgm_workspace": [C.POINTER(PgmMech), i32, i32, C.POINTER(i64)],
     "cgen_pgm_nll_fwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp],
     "cgen_pgm_nll_fwd_bwd": [C.POINTER(PgmMech), i32, vp, i32, i64, vp, i32, vp, vp, vp, vp, i64, vp],

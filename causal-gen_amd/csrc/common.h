@@ -227,6 +227,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* sm) {
 //   978              DGaussNet.sample (vae.py)
 //   979              the config-1 model's samplers (simple_vae.py)
 //   980              cgen_batch_augment's crop / flip draws (keyed by data set row)
+//   981 .. 988       Dropout of the eight residual blocks of cgen_resnet_train_fwd (csrc/predictor_resnet_train.inc)
 #define CGEN_STREAM_AUGMENT 980u
 struct Philox {
   static __device__ __forceinline__ void round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {

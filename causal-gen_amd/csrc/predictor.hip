@@ -1020,3 +1020,4 @@ extern "C" int cgen_predictor_tiled_bwd(const cgen_pred_head* heads, int32_t nhe
 #include "predictor_train.inc"
 #include "predictor_mlp.inc"
 #include "predictor_resnet.inc"
+#include "predictor_resnet_train.inc"

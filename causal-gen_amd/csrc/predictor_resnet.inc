@@ -13,6 +13,8 @@
 //   rn_gnb_apply                dx of the GroupNorm, and the masked g itself for the residual fork
 // Lanes own one 16-byte channel quad of a pixel (a group is 1, 2 or 4 quads).  Every sum runs in a fixed order: per-thread over
 // its pixels, then over the threads of the group by the group's thread through LDS, then over the chunks by one thread.  No atomics.
+// The two launch plans (rn_forward, rn_backward) take an optional RnTrain: the training arms of csrc/predictor_resnet_train.inc
+// (Dropout, parameter gradients).  Without it they are the eval plans, launch for launch.
 namespace cgen {
 namespace {
 
@@ -523,7 +525,17 @@ inline void rn_block_in(const RnPlan& p, int k, int64_t& off, int& cin, int& hin
   hin = rn_has_ds(k) ? p.hs[s - 1] : p.hs[s];
 }
 
-int rn_forward(const RnPlan& p, const cgen_resnet_args* a, const float* x, float* ws, float* terms, float* outs, hipStream_t st) {
+// The training arms of the two plans (csrc/predictor_resnet_train.inc).  tr == nullptr: the eval plans, launch for launch.
+struct RnTrain;
+int rn_tr_dropout(const RnTrain& tr, const RnPlan& p, int k, float* ws, hipStream_t st);
+int rn_tr_unscale(const RnTrain& tr, const RnPlan& p, int k, float* g, hipStream_t st);
+int rn_tr_gn(const RnTrain& tr, const RnPlan& p, const cgen_resnet_args* a, int i, const float* g, const float* y, float* ws, hipStream_t st);
+int rn_tr_wgrad(const RnTrain& tr, const RnPlan& p, int i, cgen_view seg, const float* gout, float* ws, hipStream_t st);
+int rn_tr_tail(const RnTrain& tr, const RnPlan& p, const cgen_resnet_args* a, float* ws, const float* coef, hipStream_t st);
+bool rn_tr_wants_dx(const RnTrain& tr);
+
+int rn_forward(const RnPlan& p, const cgen_resnet_args* a, const float* x, float* ws, float* terms, float* outs, hipStream_t st,
+               const RnTrain* tr = nullptr) {
   const int n = p.n;
   // stem: patches [n, h1, h1, 49 (+7 zeros)] -> 1x1 conv -> GroupNorm + ReLU -> max pool
   cgen_view xin = rn_view(const_cast<float*>(x), p.res, 1);
@@ -549,6 +561,7 @@ int rn_forward(const RnPlan& p, const cgen_resnet_args* a, const float* x, float
     }
     RN_TRY(rn_stats(p, i1, ws, st));
     RN_TRY(rn_apply(p, a, i1, nullptr, -1, ws + p.a1[k], ws, st));
+    if (tr) RN_TRY(rn_tr_dropout(*tr, p, k, ws, st));
     RN_TRY(rn_conv(p, h, 3, rn_view(ws + p.a1[k], h, c), a->img_fwd[i2], rn_view(ws + p.raw[i2], h, c), nullptr, st));
     RN_TRY(rn_stats(p, i2, ws, st));
     if (rn_has_ds(k)) {
@@ -569,7 +582,8 @@ int rn_forward(const RnPlan& p, const cgen_resnet_args* a, const float* x, float
   return check_launch("cgen_resnet (tail)");
 }
 
-int rn_backward(const RnPlan& p, const cgen_resnet_args* a, float* ws, const float* coef, float* dx, hipStream_t st) {
+int rn_backward(const RnPlan& p, const cgen_resnet_args* a, float* ws, const float* coef, float* dx, hipStream_t st,
+                const RnTrain* tr = nullptr, const float* x = nullptr) {
   const int n = p.n;
   float* G0 = ws + p.g[0];  // gradient w.r.t. the current block's output
   float* G1 = ws + p.g[1];
@@ -579,6 +593,7 @@ int rn_backward(const RnPlan& p, const cgen_resnet_args* a, float* ws, const flo
   t.coef = coef; t.g = G0;
   hipLaunchKernelGGL(rn_tail_bwd, dim3(n), dim3(256), 0, st, t);
   RN_TRY(check_launch("cgen_resnet (tail backward)"));
+  if (tr) RN_TRY(rn_tr_tail(*tr, p, a, ws, coef, st));
   for (int k = 7; k >= 0; --k) {
     const int s = k / 2, c = 64 << s, h = p.hs[s], i1 = rn_conv1(k), i2 = rn_conv2(k);
     int64_t in;
@@ -586,16 +601,33 @@ int rn_backward(const RnPlan& p, const cgen_resnet_args* a, float* ws, const flo
     rn_block_in(p, k, in, cin, hin);
     // bn2: G0 -> d raw2 in G1; G0 becomes the masked gradient, which is also the identity branch's
     RN_TRY(rn_gn_bwd(p, a, i2, G0, ws + p.y[k], G1, G0, ws, st));
+    if (tr) {  // (every weight gradient reads d raw in G1 before the next rn_gn_bwd overwrites it: one stream, in order)
+      RN_TRY(rn_tr_gn(*tr, p, a, i2, G0, ws + p.y[k], ws, st));
+      RN_TRY(rn_tr_wgrad(*tr, p, i2, rn_view(ws + p.a1[k], h, c), G1, ws, st));
+    }
     RN_TRY(rn_conv(p, h, 3, rn_view(G1, h, c), a->img_dg[i2], rn_view(G2, h, c), nullptr, st));  // -> gradient w.r.t. a1
+    if (tr) RN_TRY(rn_tr_unscale(*tr, p, k, G2, st));                                             // (Dropout's 1 / (1 - p))
     RN_TRY(rn_gn_bwd(p, a, i1, G2, ws + p.a1[k], G1, nullptr, ws, st));                           // -> d raw1
+    if (tr) RN_TRY(rn_tr_gn(*tr, p, a, i1, G2, ws + p.a1[k], ws, st));
     if (rn_has_ds(k)) {
       const int id = rn_ds(s);
+      if (tr) {  // the patches again (the forward's are long overwritten), into col before the data gradient below takes it
+        RN_TRY(cgen_im2col_strided(CGEN_F32, n, hin, hin, 3, 2, 1, h, h, rn_view(ws + in, hin, cin), rn_view(ws + p.col, h, 9 * cin), st));
+        RN_TRY(rn_tr_wgrad(*tr, p, i1, rn_view(ws + p.col, h, 9 * cin), G1, ws, st));
+      }
       RN_TRY(rn_conv(p, h, 1, rn_view(G1, h, c), a->img_dg[i1], rn_view(ws + p.col, h, 9 * cin), nullptr, st));
       RN_TRY(cgen_col2im_strided(CGEN_F32, n, hin, hin, 3, 2, 1, h, h, rn_view(ws + p.col, h, 9 * cin), rn_view(G2, hin, cin), 0, st));
       RN_TRY(rn_gn_bwd(p, a, id, G0, ws + p.y[k], G1, nullptr, ws, st));  // (G0 is masked already: masking again changes nothing)
+      if (tr) {
+        cgen_view even = rn_view(ws + in, hin, cin);  // as the forward reads it
+        even.sh *= 2; even.sw *= 2;
+        RN_TRY(rn_tr_gn(*tr, p, a, id, G0, ws + p.y[k], ws, st));
+        RN_TRY(rn_tr_wgrad(*tr, p, id, even, G1, ws, st));
+      }
       RN_TRY(rn_conv(p, h, 1, rn_view(G1, h, c), a->img_dg[id], rn_view(ws + p.col, h, cin), nullptr, st));
       RN_TRY(cgen_col2im_strided(CGEN_F32, n, hin, hin, 1, 2, 0, h, h, rn_view(ws + p.col, h, cin), rn_view(G2, hin, cin), 1, st));
     } else {
+      if (tr) RN_TRY(rn_tr_wgrad(*tr, p, i1, rn_view(ws + in, h, cin), G1, ws, st));
       const cgen_view idn = rn_view(G0, h, c);
       RN_TRY(rn_conv(p, h, 3, rn_view(G1, h, c), a->img_dg[i1], rn_view(G2, h, cin), &idn, st));
     }
@@ -608,6 +640,13 @@ int rn_backward(const RnPlan& p, const cgen_resnet_args* a, float* ws, const flo
     RN_TRY(check_launch("cgen_resnet (max pool backward)"));
   }
   RN_TRY(rn_gn_bwd(p, a, 0, G1, ws + p.stem_act, G2, nullptr, ws, st));
+  if (tr) {
+    RN_TRY(rn_tr_gn(*tr, p, a, 0, G1, ws + p.stem_act, ws, st));
+    RN_TRY(cgen_im2col_strided(CGEN_F32, n, p.res, p.res, 7, 2, 3, p.h1, p.h1, rn_view(const_cast<float*>(x), p.res, 1),
+                               rn_view(ws + p.col, p.h1, 49, 56), st));
+    RN_TRY(rn_tr_wgrad(*tr, p, 0, rn_view(ws + p.col, p.h1, 49, 56), G2, ws, st));
+    if (!rn_tr_wants_dx(*tr)) return CGEN_OK;
+  }
   RN_TRY(rn_conv(p, p.h1, 1, rn_view(G2, p.h1, 64), a->img_dg[0], rn_view(ws + p.col, p.h1, 49, 56), nullptr, st));
   cgen_view gcol = rn_view(ws + p.col, p.h1, 49, 56);
   gcol.cpad = 0;

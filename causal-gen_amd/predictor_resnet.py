@@ -5,7 +5,8 @@
 ``Linear`` on the pooled features; ``encoder_a`` also sees ``finding``.  The reference runs the trunk once per head; here it runs
 ONCE per call and feeds the four heads -- same numbers, a quarter of the work (csrc/predictor_resnet.inc, ``cgen_resnet_*``).
 The predictor is frozen and in eval mode (Dropout is the identity): forward, likelihoods, ``predict`` and the input gradient
-``d aux / d cf_x``.  Training these heads is not built.
+``d aux / d cf_x``.  Training these heads is ``predictor_resnet_train.ChestPredictorTrainStep``'s business, which works on this
+module's parameters from outside: ``train()`` here still leaves eval mode on and ``_heads()`` still raises.
 
 The modules are parameter holders with the reference's names, so that the 248 ``encoder_*`` keys of a reference checkpoint load
 strictly; ``torch_outputs`` is the same network in plain torch ops on those parameters (any device, any dtype) for the CPU tests
@@ -169,14 +170,10 @@ class ChestPredictor(_AnticausalPredictor):
         return (str(device),) + tuple(p._version for p in ps) + tuple(p.data_ptr() for p in ps)
 
     @torch.no_grad()
-    def _images(self, device):
-        """The weight images (cgen_weight_prep modes 0 / 1, f32), GroupNorm parameters and head weights on ``device``; rebuilt
-        when a parameter's version or address changes."""
-        key = self._state_key(device)
-        rt = self.__dict__.get("_rt")
-        if rt is not None and rt[0] == key:
-            return rt[1]
-        lib = _lib.require_gpu()
+    def _weight_tables(self, device):
+        """The 40 weight images (cgen_weight_prep modes 0 / 1, f32; empty) and the launch's descriptor and chunk tables on
+        ``device``.  ``srcs`` are the f32 parameters the descriptors read: the parameters themselves where they already are
+        contiguous f32 tensors on ``device``."""
         dev32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
         sites = _conv_sites(self.encoder_s.resnet)
         descs, srcs, fwd, dg = [], [], [], []
@@ -205,8 +202,23 @@ class ChestPredictor(_AnticausalPredictor):
             cidx += list(range(nch))
         tab = torch.frombuffer(bytearray(bytes((_lib.WprepDesc * len(descs))(*descs))), dtype=torch.uint8).to(device)
         cs, ci_ = (torch.tensor(v, dtype=torch.int32, device=device) for v in (csite, cidx))
-        lib.weight_prep(tab.data_ptr(), cs.data_ptr(), ci_.data_ptr(), len(csite), torch.cuda.current_stream(device).cuda_stream)
-        out = {"fwd": fwd, "dg": dg, "gamma": [dev32(n.weight) for _, n, _ in sites], "beta": [dev32(n.bias) for _, n, _ in sites],
+        return {"fwd": fwd, "dg": dg, "srcs": srcs, "tab": tab, "csite": cs, "cidx": ci_, "nchunks": len(csite)}
+
+    @torch.no_grad()
+    def _images(self, device):
+        """The weight images (cgen_weight_prep modes 0 / 1, f32), GroupNorm parameters and head weights on ``device``; rebuilt
+        when a parameter's version or address changes."""
+        key = self._state_key(device)
+        rt = self.__dict__.get("_rt")
+        if rt is not None and rt[0] == key:
+            return rt[1]
+        lib = _lib.require_gpu()
+        dev32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        sites = _conv_sites(self.encoder_s.resnet)
+        wt = self._weight_tables(device)
+        lib.weight_prep(wt["tab"].data_ptr(), wt["csite"].data_ptr(), wt["cidx"].data_ptr(), wt["nchunks"],
+                        torch.cuda.current_stream(device).cuda_stream)
+        out = {"fwd": wt["fwd"], "dg": wt["dg"], "gamma": [dev32(n.weight) for _, n, _ in sites], "beta": [dev32(n.bias) for _, n, _ in sites],
                "fc_w": [dev32(e.fc.weight) for e in self._encoders()], "fc_b": [dev32(e.fc.bias) for e in self._encoders()]}
         self.__dict__["_rt"] = (key, out)
         return out

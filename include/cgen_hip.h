@@ -780,6 +780,43 @@ int cgen_resnet_fwd(const cgen_resnet_args* a, int32_t n, const float* x, float*
 int cgen_resnet_bwd(const cgen_resnet_args* a, int32_t n, float* ws, int64_t ws_floats, const float* coef_dev, float* dx,
                     cgen_stream_t);
 
+/* ------------------------------------------------------------------ ChestPGM's anticausal heads, TRAINING (additive in ABI 411; csrc/predictor_resnet_train.inc)
+ * The same network with CustomBlock's Dropout(p) after relu(bn1) of each of the eight blocks and every parameter gradient:
+ *   a1[k] = keep ? relu(gn(raw)) * (1 / (1 - p)) : 0, keep = (u >= p) with u the Philox4x32-10 uniform of (rng state, stream
+ *   981 + k, counter (image << 32 | channel quad of the image's NHWC map), word = channel & 3): an image's mask does not depend on
+ *   n.  The forward does NOT advance the state (cgen_rng_advance does, between steps).  p_dropout == 0 launches exactly what
+ *   cgen_resnet_fwd launches and leaves the same bits.  Deviation from the reference: it runs the trunk once per head and so
+ *   draws four independent masks per step; here the trunk runs once, with one mask.
+ * The backward is cgen_resnet_bwd's launch sequence (dx, when asked for, has its bits) with, beside it, per conv site: the f32
+ * split-K weight gradient of the library (cgen_conv2d_wgrad + cgen_wgrad_reduce into the OIHW gradient; the stem and the stride-2
+ * 3x3 convs as ks-1 problems on patches rebuilt by cgen_im2col_strided, the 1x1/s2 convs on the even-pixel view) and the GroupNorm
+ * parameter gradients (per-(image, chunk, channel) partials, then one fixed tree per channel quad); and the four Linears' gradients.
+ * Every gradient is OVERWRITTEN with d (coef_dev[0] * sum of terms) / d parameter.
+ * An image that leaves a non-finite GroupNorm statistic (a NaN or Inf in x or in a weight) gets NaN for its four terms: the eval
+ * kernels' ReLU maps NaN to 0, torch's keeps it, and a training step must see such a batch as the reference sees it.
+ * The workspace starts with cgen_resnet_workspace's layout (cgen_resnet_site applies) and is larger.  One stream, no allocation,
+ * synchronisation or host read, fixed-order sums without atomics, bit-identical reruns, capturable -- as cgen_resnet_*. */
+typedef struct cgen_resnet_train_args {
+  cgen_resnet_args net;
+  float* gw[CGEN_RESNET_CONVS];      /* OIHW gradient of each conv, 16-byte aligned */
+  float* ggamma[CGEN_RESNET_CONVS];  /* GroupNorm weight / bias gradients, 16-byte aligned */
+  float* gbeta[CGEN_RESNET_CONVS];
+  float* gfc_w[4];                   /* as fc_w / fc_b, 4-byte aligned */
+  float* gfc_b[4];
+  const uint64_t* rng;               /* device {seed, offset}, what cgen_rng_advance moves */
+  float p_dropout;                   /* in [0, 1) */
+  int32_t reserved;
+} cgen_resnet_train_args;
+int cgen_resnet_train_workspace(int32_t n, int32_t res, int64_t* floats);
+int cgen_resnet_train_fwd(const cgen_resnet_train_args* a, int32_t n, const float* x, float* ws, int64_t ws_floats, float* terms,
+                          float* outs, float* loss, cgen_stream_t);
+/* x: the forward's image (the stem's patches are rebuilt from it); dx optional (NULL: the stem's data gradient is not computed). */
+int cgen_resnet_train_bwd(const cgen_resnet_train_args* a, int32_t n, const float* x, float* ws, int64_t ws_floats,
+                          const float* coef_dev, float* dx, cgen_stream_t);
+/* keep [n, h, h, c] (NHWC, one byte per element: 1 = kept) = the decisions the forward takes for block k = 0..7 under this state
+ * and p, from the same device function (tests, debugging). */
+int cgen_resnet_dropout_keep(const uint64_t* rng, float p_dropout, int32_t n, int32_t res, int32_t block, uint8_t* keep, cgen_stream_t);
+
 /* ------------------------------------------------------------------ scalar predictor head, TRAINING mode (additive in ABI 411; csrc/predictor_mlp.inc)
  * pgm/layers.py MLP in train mode (layers.py:46-59), scored as flow_pgm.py:260-267 scores encoder_a: q(a | b, v) = Normal(MLP(b, v)).
  *   mlp.0 Linear nin -> w (no bias), mlp.1 BatchNorm1d(w), LeakyReLU(0.01), mlp.3 Linear w -> w (no bias), mlp.4 BatchNorm1d(w),
