@@ -778,6 +778,24 @@ __global__ __launch_bounds__(256, 2) void blk3_pair_kernel(B3P pa, B3P pb, const
   blk3_body<PRE, NB, NPG, SM, TH, REM>(p, second ? (int)blockIdx.x - na : (int)blockIdx.x, second ? (int)gridDim.x - na : na, koff);
 }
 
+// The forward pass of the same two Blocks: two DIFFERENT instances in one launch (the posterior's 32 output channels are one
+// 32-channel pair, the prior's 2 z + width are three or more; twelve-row tiles where they save the prior a round), the same
+// bottleneck.  Workgroups 0 .. na - 1 run instance A on the first record, the rest instance B on the second; each is the body of the
+// single launch on the same record, so the bits are the single launches'.  Only the combinations the decoder layers of the presets
+// plan to are instantiated (b3_fwd_pair_nb): two bodies per kernel share the instruction cache (LABNOTES 10.5).
+template <int NB, int NPG_A, int TH_A, int NPG_B, int TH_B>
+__global__ __launch_bounds__(256, 2) void blk3_fwd_pair_kernel(B3P pa, B3P pb, const int na) {
+  (void)pa; (void)pb;
+  constexpr size_t off_b = (sizeof(B3P) + alignof(B3P) - 1) / alignof(B3P) * alignof(B3P);
+  typedef const B3P __attribute__((address_space(4)))* kp_ptr;
+  const char __attribute__((address_space(4)))* const ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+  if ((int)blockIdx.x < na) {
+    blk3_body<true, NB, NPG_A, 0, TH_A, false>(*(const B3P*)(kp_ptr)ka, (int)blockIdx.x, na, 0);
+  } else {
+    blk3_body<true, NB, NPG_B, 0, TH_B, false>(*(const B3P*)(kp_ptr)(ka + off_b), (int)blockIdx.x - na, (int)gridDim.x - na, (int)off_b);
+  }
+}
+
 // ============================================================================= small images (<= 14 pixels wide: 12x12, 6x6, ...)
 // The top of both hierarchies: ~1 % of a step's FLOPs, 22 % of its time as two latency-bound conv launches per Block (bottlenecks of
 // 40 / 48 channels, which the tile kernel above does not take).  Here ONE workgroup owns R output rows of ONE image -- R = the most
@@ -1165,6 +1183,8 @@ __global__ __launch_bounds__(64 * B3S_NW, 4) void blk3s_kernel(B3P p) {
 }
 // two independent data-gradient problems in one launch (as blk3_pair_kernel): 128 + 128 workgroups of a decoder layer's posterior and
 // prior Blocks fill the chip that either alone leaves half empty
+// (PRE: the forward pass of the same two Blocks, as blk3_fwd_pair_kernel -- the small-image body is one instance for every width)
+template <bool PRE>
 __global__ __launch_bounds__(64 * B3S_NW, 4) void blk3s_pair_kernel(B3P pa, B3P pb, const int na) {
   (void)pa; (void)pb;
   const bool second = (int)blockIdx.x >= na;
@@ -1172,7 +1192,7 @@ __global__ __launch_bounds__(64 * B3S_NW, 4) void blk3s_pair_kernel(B3P pa, B3P 
   const int koff = second ? (int)off_b : 0;
   typedef const B3P __attribute__((address_space(4)))* kp_ptr;
   const B3P& p = *(const B3P*)(kp_ptr)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + koff);
-  blk3s_body<false>(p, second ? (int)blockIdx.x - na : (int)blockIdx.x, second ? (int)gridDim.x - na : na, koff);
+  blk3s_body<PRE>(p, second ? (int)blockIdx.x - na : (int)blockIdx.x, second ? (int)gridDim.x - na : na, koff);
 }
 
 // ============================================================================= wide images, narrow channels (96x96, 192x192)
@@ -1803,22 +1823,49 @@ static void b3_pair_nb(const B3P& pa, const B3P& pb, const B3Launch& La, const B
   else if (NB <= 3 && La.th == 12) { if constexpr (NB <= 3) b3_pair_inst<NB, 4, 12>(pa, pb, La, Lb, st); }
   else b3_pair_inst<NB, 4>(pa, pb, La, Lb, st);
 }
+// forward pair launch: instance A (the posterior Block: one 32-channel pair of outputs, eight-row tiles) and instance B (the prior
+// Block: three or more pairs, eight- or twelve-row tiles) on one bottleneck width.  What the decoder layers of the presets plan to
+// (ukbb192 / mimic224 at 24^2 / 28^2: NB 4, (1, 8) + (4, 8); at 48^2 / 56^2: NB 3, (1, 8) + (4, 12) or (4, 8) by batch); nothing else
+// is compiled, and b3_pair_plan declines the rest.
+template <int NB, int NPG_B, int TH_B>
+static void b3_fwd_pair_inst(const B3P& pa, const B3P& pb, const B3Launch& La, const B3Launch& Lb, hipStream_t st) {
+  (void)hipFuncSetAttribute((const void*)blk3_fwd_pair_kernel<NB, 1, 8, NPG_B, TH_B>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL((blk3_fwd_pair_kernel<NB, 1, 8, NPG_B, TH_B>), dim3(La.grid + Lb.grid), dim3(256), std::max(La.lds, Lb.lds), st, pa, pb, La.grid);
+}
+static bool b3_fwd_pair_served(int nb, const B3Launch& La, const B3Launch& Lb) {
+  if (La.npg != 1 || La.th != 8 || Lb.npg != 4) return false;
+  return (nb == 4 && Lb.th == 8) || (nb == 3 && (Lb.th == 8 || Lb.th == 12));
+}
+static void b3_fwd_pair_launch(const B3P& pa, const B3P& pb, const B3Launch& La, const B3Launch& Lb, hipStream_t st) {
+  if (pa.b / 8 == 4) b3_fwd_pair_inst<4, 4, 8>(pa, pb, La, Lb, st);
+  else if (Lb.th == 12) b3_fwd_pair_inst<3, 4, 12>(pa, pb, La, Lb, st);
+  else b3_fwd_pair_inst<3, 4, 8>(pa, pb, La, Lb, st);
+}
+
 // 0: the two problems cannot share a launch
 static int b3_pair_plan(const cgen_block3_args* a, const cgen_block3_args* b, B3P& pa, B3P& pb, B3Launch& La, B3Launch& Lb) {
-  if (!a || !b || a->pre_act || b->pre_act || !a->mid_aux.p || !b->mid_aux.p) return 0;
+  if (!a || !b || (a->pre_act != 0) != (b->pre_act != 0)) return 0;
+  const bool pre = a->pre_act != 0;
+  if (pre) {  // forward: a decoder layer's posterior (a) and prior (b) Block -- one image size, one batch, no residual, one output each
+    if (a->mid_aux.p || b->mid_aux.p || a->n != b->n || a->h != b->h || a->w != b->w || a->nout != 1 || b->nout != 1) return 0;
+    if (a->o[0].res1.p || b->o[0].res1.p) return 0;
+  } else if (!a->mid_aux.p || !b->mid_aux.p) return 0;
   if (!b3_fill(a, pa) || !b3_fill(b, pb)) return 0;
   if (pa.rows || pb.rows) return 0;
+  if (pre && pa.b != pb.b) return 0;
   if (pa.small || pb.small) {
     La.grid = pa.ntiles; Lb.grid = pb.ntiles;
     La.lds = b3s_lds(pa); Lb.lds = b3s_lds(pb);
     La.npg = Lb.npg = 0; La.sm = Lb.sm = 0; La.th = Lb.th = 0;
+    if (pre && (pa.o[0].res_rem || pb.o[0].res_rem)) return 0;
     return (pa.small && pb.small && !pa.o[0].out_rem && !pb.o[0].out_rem) ? 1 : 0;
   }
   const int ta = pa.ntiles, tb = pb.ntiles;  // (eight-row tiles: the cap decision below only needs "more than one tile per CU or not")
   La = b3_plan(pa, tb);
   Lb = b3_plan(pb, ta);
-  if (La.sm || Lb.sm || La.npg != Lb.npg || La.th != Lb.th || pa.b != pb.b) return 0;
   if (pa.o[0].out_rem || pa.o[0].res_rem || pb.o[0].out_rem || pb.o[0].res_rem) return 0;
+  if (pre) return (!La.sm && !Lb.sm && b3_fwd_pair_served(pa.b / 8, La, Lb)) ? 1 : 0;
+  if (La.sm || Lb.sm || La.npg != Lb.npg || La.th != Lb.th || pa.b != pb.b) return 0;
   return 1;
 }
 
@@ -1838,14 +1885,41 @@ extern "C" int cgen_block3_pair_supported(const cgen_block3_args* a, const cgen_
   return b3_pair_plan(a, b, pa, pb, La, Lb);
 }
 
+// The plan of a pair launch, for tools and tests (host code: the same answer with and without a GPU).  Returns what
+// cgen_block3_pair_supported returns; when that is 1, out[0 .. 7] = bottleneck / 8, small instance (0 / 1), then per record the
+// phase-B wave split (NPG), the tile rows (TH) and the workgroups.
+extern "C" int cgen_block3_pair_plan(const cgen_block3_args* a, const cgen_block3_args* b, int* out) {
+  B3P pa, pb;
+  B3Launch La, Lb;
+  if (!b3_pair_plan(a, b, pa, pb, La, Lb)) return 0;
+  if (out) {
+    out[0] = pa.b / 8; out[1] = pa.small;
+    out[2] = La.npg; out[3] = La.th; out[4] = La.grid;
+    out[5] = Lb.npg; out[6] = Lb.th; out[7] = Lb.grid;
+  }
+  return 1;
+}
+
 extern "C" int cgen_block3_pair(const cgen_block3_args* a, const cgen_block3_args* b, cgen_stream_t stream) {
   B3P pa, pb;
   B3Launch La, Lb;
-  CGEN_REQUIRE(b3_pair_plan(a, b, pa, pb, La, Lb), "cgen_block3_pair: the two problems do not plan to the same data-gradient instance (ask cgen_block3_pair_supported first)");
+  CGEN_REQUIRE(b3_pair_plan(a, b, pa, pb, La, Lb), "cgen_block3_pair: the two problems do not plan to instances that share a launch (ask cgen_block3_pair_supported first)");
+  const bool pre = a->pre_act != 0;
   if (pa.small) {
-    (void)hipFuncSetAttribute((const void*)blk3s_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(blk3s_pair_kernel, dim3(La.grid + Lb.grid), dim3(64 * B3S_NW), std::max(La.lds, Lb.lds), (hipStream_t)stream, pa, pb, La.grid);
+    if (pre) {
+      (void)hipFuncSetAttribute((const void*)blk3s_pair_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipLaunchKernelGGL(blk3s_pair_kernel<true>, dim3(La.grid + Lb.grid), dim3(64 * B3S_NW), std::max(La.lds, Lb.lds), (hipStream_t)stream, pa, pb, La.grid);
+    } else {
+      (void)hipFuncSetAttribute((const void*)blk3s_pair_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipLaunchKernelGGL(blk3s_pair_kernel<false>, dim3(La.grid + Lb.grid), dim3(64 * B3S_NW), std::max(La.lds, Lb.lds), (hipStream_t)stream, pa, pb, La.grid);
+    }
     return check_launch("cgen_block3_pair(small)");
+  }
+  static const bool trace = getenv("CGEN_CONV_TRACE") != nullptr;
+  if (pre) {
+    b3_fwd_pair_launch(pa, pb, La, Lb, (hipStream_t)stream);
+    if (trace) fprintf(stderr, "blk3 pair[fwd] %dx%dx%d b %d | grids %d + %d, lds %zu, tile rows %d + %d\n", a->n, a->h, a->w, pa.b, La.grid, Lb.grid, std::max(La.lds, Lb.lds), La.th, Lb.th);
+    return check_launch("cgen_block3_pair(fwd)");
   }
   switch (pa.b / 8) {
     case 1: b3_pair_nb<1>(pa, pb, La, Lb, (hipStream_t)stream); break;
@@ -1853,7 +1927,6 @@ extern "C" int cgen_block3_pair(const cgen_block3_args* a, const cgen_block3_arg
     case 3: b3_pair_nb<3>(pa, pb, La, Lb, (hipStream_t)stream); break;
     default: b3_pair_nb<4>(pa, pb, La, Lb, (hipStream_t)stream); break;
   }
-  static const bool trace = getenv("CGEN_CONV_TRACE") != nullptr;
   if (trace) fprintf(stderr, "blk3 pair[bwd] %dx%dx%d b %d | grids %d + %d, lds %zu, tile rows %d\n", a->n, a->h, a->w, pa.b, La.grid, Lb.grid, std::max(La.lds, Lb.lds), La.th);
   return check_launch("cgen_block3_pair");
 }

@@ -323,6 +323,22 @@ class Engine(WgradMixin):
         self.blk3_pair = os.environ.get("CGEN_BLK3_PAIR", "1") != "0"
         self._blk3 = PairSlot(self, self._block3_single, lambda h, a: self.lib.block3_pair(C.byref(h), C.byref(a), self.stream),
                               lambda h, a: self.lib.block3_pair_supported(C.byref(h), C.byref(a)))
+        # The FORWARD launches of the same two Blocks the same way (cgen_block3_pair with pre_act = 1 on both records): HVAE._decode arms
+        # this slot for a layer whose pair the kernel is expected to serve (pairing.fwd_pair_expected), holds the posterior Block's launch
+        # and sends the pair at the prior Block's launch point, all on the main stream -- such a layer has no fork and no join.
+        # CGEN_BLK3_FWD_PAIR=0: the two-queue path, launch for launch.  CGEN_BLK3_FWD_PAIR_RES: the image sides served (ranges as
+        # CGEN_BLK3_RES); CGEN_BLK3_FWD_PAIR_FIRST: with _SERIAL=0, the largest side at which the FIRST layer of a resolution pairs too
+        # (its z is upsampled on the main stream then, in front of the pair).  CGEN_BLK3_FWD_PAIR_SERIAL (1): in a decoder pass that pairs any
+        # layer, the layers the pair does not serve (1x1, 96x96, the first of a resolution above _FIRST) run their prior chain in line on
+        # the main stream as well -- the pass captures no fork at all.  Measured (LABNOTES 32.4, ukbb192, profiler off): pairs beside
+        # the remaining forks 12.43 ms per step against 12.42 without pairs; pairs and no fork 12.17 against 12.38.  0: those layers fork as before.
+        self.blk3_fwd_pair = int(os.environ.get("CGEN_BLK3_FWD_PAIR", "1")) if self.dt == F16 else 0
+        self.blk3_fwd_pair_serial = os.environ.get("CGEN_BLK3_FWD_PAIR_SERIAL", "1") != "0"
+        self.blk3_fwd_pair_res = self._side_ranges(os.environ.get("CGEN_BLK3_FWD_PAIR_RES", "4-64"))
+        self.blk3_fwd_pair_first = int(os.environ.get("CGEN_BLK3_FWD_PAIR_FIRST", "24"))
+        self._blk3f = PairSlot(self, self._block3_fwd_single, lambda h, a: self.lib.block3_pair(C.byref(h), C.byref(a), self.stream),
+                               lambda h, a: self.lib.block3_pair_supported(C.byref(h), C.byref(a)))
+        self._fwd_pair_ok = {}  # (layer, batch) -> pairing.fwd_pair_expected's answer
         # ... and the same for data-gradient convs on the small-image path (cgen_conv2d_pair): the two gradient outputs of one conv
         # (cat[z, p_feat] of z_feat_proj, cat[h, pa, acts] of an unfused posterior Block), and the second convs of an unfused
         # posterior / prior Block pair, which backward() brings next to each other
@@ -408,6 +424,8 @@ class Engine(WgradMixin):
     blk3_pairs = property(lambda self: self._blk3.pairs, lambda self, v: setattr(self._blk3, "pairs", v))
     blk4_pairs = property(lambda self: self._blk4.pairs, lambda self, v: setattr(self._blk4, "pairs", v))
     conv_pairs = property(lambda self: self._conv.pairs, lambda self, v: setattr(self._conv, "pairs", v))
+    blk3_fwd_pairs = property(lambda self: self._blk3f.pairs, lambda self, v: setattr(self._blk3f, "pairs", v))  # ... of the forward passes since begin()
+    f16 = property(lambda self: self.dt == F16)
 
     @property
     def trunk_rem(self):
@@ -446,7 +464,7 @@ class Engine(WgradMixin):
         self._wg_events = []
         self._wg_reduced, self._wg_seen = 0, set()
         self._riders = {}
-        for slot in (self._blk3, self._blk4, self._conv):  # (a pass that ended in an exception may have left a launch held)
+        for slot in (self._blk3, self._blk4, self._conv, self._blk3f):  # (a pass that ended in an exception may have left a launch held)
             slot.reset()
         self.pgrad_init = set()
         self._pnhwc, self._pgrad_tmp = {}, {}
@@ -456,7 +474,7 @@ class Engine(WgradMixin):
         self._wg_forked = False
         self._split_done = False
         self.passes = 0
-        self.lat_tails_fwd = self.lat_tails_det_fwd = 0
+        self.lat_tails_fwd = self.lat_tails_det_fwd = self.blk3_fwd_pairs = 0
         self.like_heads = 0
         self.stream = torch.cuda.current_stream(self.device).cuda_stream
 
@@ -818,8 +836,12 @@ class Engine(WgradMixin):
         sup = self.lib.block3_supported(C.byref(a))
         if not sup or (need_rows and sup != 2):  # (2: the row-streaming instance serves it)
             return None  # (the two tensors just allocated are simply not used: the arena is reset per step)
-        if not self._ablated(x0):
-            self._timed("conv_fwd", (site1, site2), x0, lambda: self.lib.block3(C.byref(a), self.stream))
+        if self._ablated(x0):
+            self._blk3f.flush()
+        else:
+            # through the forward pair slot: launched here, or -- armed by HVAE._decode -- held for the layer's other Block.  It writes
+            # out and the bottleneck and reads the segments (storage identity: a pair must not touch each other's)
+            self._blk3f.submit(a, {id(out.base), id(t.base)}, {id(sg.base) for sg in segs}, ((site1, site2), x0))
         if self.recording:
             if self._dbg_names is not None:
                 self._dbg_names[id(out.base)] = site2.name
@@ -829,6 +851,10 @@ class Engine(WgradMixin):
                 self.tape.append((self._bw_conv, (site1, segs, ACT_RELU, t, None, None), self._bw_tag))
                 self.tape.append((self._bw_conv, (site2, [t], ACT_RELU, out, res1, None), self._bw_tag))
         return out
+
+    def _block3_fwd_single(self, a, info):
+        sites, x0 = info
+        self._timed("conv_fwd", sites, x0, lambda: self.lib.block3(C.byref(a), self.stream))
 
     def _ghost(self, n, h, w, c):
         """The handle of a tensor that is never materialised (no storage: a NULL view): it stands on the tape for its GRADIENT buffer."""
@@ -1599,6 +1625,15 @@ class Engine(WgradMixin):
         finally:
             self.stream = old
             self._in_side = False
+            self._bw_tag = old_tag
+
+    def side_tagged(self, fn, bw=1):
+        """Run `fn()` on the CURRENT stream with its tape entries tagged as `on_side(fn, bw)` tags them (a prior Block that shares the
+        posterior Block's launch: no side stream, the same tape)."""
+        old_tag, self._bw_tag = self._bw_tag, bw
+        try:
+            return fn()
+        finally:
             self._bw_tag = old_tag
 
     def join_side(self):

@@ -1,8 +1,12 @@
-"""Pair launches of the backward pass: a data-gradient launch is HELD until a partner reaches its own launch point, then the two
-share one launch (cgen_block3_pair / cgen_block4_pair / cgen_conv2d_pair) or go out one after the other.  One `PairSlot` per
-kernel family; `may_pair` is backward()'s rule for arming a fused Block's slot.  Host logic only (no torch, no library):
-tests/test_pairing.py drives it with fakes.  DESIGN.md, "Pair launch"."""
+"""Pair launches: a launch is HELD until a partner reaches its own launch point, then the two share one launch (cgen_block3_pair /
+cgen_block4_pair / cgen_conv2d_pair) or go out one after the other.  One `PairSlot` per kernel family and direction; `may_pair` is
+backward()'s rule for arming a fused Block's slot, `fwd_pair_expected` the decoder's rule for a layer's posterior and prior Blocks
+in the forward pass.  Host logic only (no torch; the library only through the `lib` handed in): tests/test_pairing.py and
+tests/test_pairing_fwd.py drive it with fakes.  DESIGN.md, "Pair launch"."""
+import ctypes as C
 from collections import namedtuple
+
+FwdBlock = namedtuple("FwdBlock", "light nconv residual down seg_c b co")  # what the rule needs to know of a Block (vae.Block)
 
 # args of a fused Block's tape entry (fn, args, tag); fn(*args) is its backward.  `mids`: the bottleneck tensors.
 BlockRec = namedtuple("BlockRec", "sites segs mids out res1")
@@ -81,3 +85,54 @@ class PairSlot:
         if held is not None:
             self._single(held[0], held[4])
             held[5]()
+
+
+def _in_ranges(v, ranges):
+    return not ranges or any(lo <= v <= hi for lo, hi in ranges)
+
+
+def fwd_pair_expected(eng, libmod, n, res, first, post, prior):
+    """Will the forward pass of a stochastic decoder layer at `res` x `res`, batch `n`, send its posterior Block `post` and its prior
+    Block `prior` (FwdBlock each) as ONE launch?  Decided before the layer runs (the layer in front of it must know whether to fork a
+    side stream ahead), from what is known then: the engine's dtype and knobs (`eng`: blk3_fwd_pair, blk3_fwd_pair_res,
+    blk3_fwd_pair_first, blk3_fwd_pair_serial, blk3_on, blk3_small, blk3_minres, blk3_res, blk3_res3, f16, lib), the resolution and the widths.  `first`:
+    the layer is the first of its resolution (its z is upsampled in front of the prior Block).  The kernel's own answer
+    (cgen_block3_pair_supported, host code) is asked on dense stand-ins of the tensors; `libmod` is causal_gen_amd._lib (the
+    argument records).  A wrong "yes" costs nothing but the pair: the slot sends the two launches singly."""
+    if not (eng.blk3_fwd_pair and eng.f16 and eng.blk3_on and _in_ranges(res, eng.blk3_fwd_pair_res)):
+        return False
+    if first and res > eng.blk3_fwd_pair_first and not eng.blk3_fwd_pair_serial:
+        return False  # (that layer keeps the fork, which hides the upsample; a pass that forks nowhere has nothing to hide it under)
+    for blk in (post, prior):
+        # Engine.block2's own conditions for the one-launch Block (the 1x1 layers and the four-conv Block never get there)
+        if not (blk.light and blk.nconv == 2 and not blk.residual and not blk.down and blk.b % 8 == 0 and blk.co % 8 == 0
+                and 1 <= len(blk.seg_c) <= 3):
+            return False
+        small = eng.blk3_small and res <= 14 and res >= 4
+        res_ok = eng.blk3_res3 if len(blk.seg_c) >= 3 else eng.blk3_res
+        tile_ok = res >= eng.blk3_minres and blk.b <= 32 and _in_ranges(res, res_ok)
+        if not ((small and blk.b <= 64) or tile_ok):
+            return False
+    return bool(eng.lib.block3_pair_supported(C.byref(fwd_probe_args(libmod, n, res, post)), C.byref(fwd_probe_args(libmod, n, res, prior))))
+
+
+def fwd_probe_args(libmod, n, res, blk, f16=1):
+    """cgen_block3_args of a forward Block on dense stand-ins of its tensors (aligned, never dereferenced by the host-side planner);
+    a segment whose width is no multiple of 8 stands for the parents: spatially constant, zero-padded to 8."""
+    a = libmod.Block3Args()
+    a.dtype, a.n, a.h, a.w, a.nseg, a.nout, a.pre_act = f16, n, res, res, len(blk.seg_c), 1, 1
+    fake = 1 << 20
+
+    def dense(c):
+        cp = -(-c // 8) * 8
+        if c % 8:
+            return libmod.View(fake, cp, 0, 0, c, cp)
+        return libmod.View(fake, res * res * cp, res * cp, cp, c, 0)
+
+    for k, c in enumerate(blk.seg_c):
+        a.seg[k] = dense(c)
+    a.w_a, a.bias_a = fake, fake
+    a.mid, a.mid_aux = dense(blk.b), libmod.NULL_VIEW
+    o = a.o[0]
+    o.w, o.bias, o.out, o.aux, o.res1 = fake, fake, dense(blk.co), libmod.NULL_VIEW, libmod.NULL_VIEW
+    return a

@@ -23,6 +23,7 @@ from torch import Tensor, nn
 from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, NULL_VIEW
 from .engine import ConvSite, Engine
+from .pairing import FwdBlock, fwd_pair_expected
 
 EPS = -9  # minimum logscale (vae.py:11)
 
@@ -118,6 +119,33 @@ def _decoder_sites(sites, dec, prefix, zd, ctx):
         if not b.q_correction:
             sites.append(ConvSite(n + ".z_feat_proj", b.z_feat_proj, [zd, w], [True, True], len(sites)))
         _block_sites(sites, n + ".conv", b.conv, [w], [True])
+
+
+def fwd_pair_layer(eng, dec, i, B):
+    """pairing.fwd_pair_expected for layer i of decoder `dec`: what `eng` (an Engine, or a stand-in with its knobs and the library)
+    is expected to do with the layer's posterior and prior Blocks at batch B.  Needs no GPU."""
+    blk = dec.blocks[i]
+    if not blk.stochastic or blk.q_correction:
+        return False
+
+    def desc(b, seg_c):
+        cs = b.convs()
+        assert sum(seg_c) == cs[0].in_channels, (seg_c, cs[0].in_channels)
+        return FwdBlock(bool(b.light), len(cs), bool(b.residual), bool(b.d), seg_c, cs[0].out_channels, cs[-1].out_channels)
+
+    w, ctx = blk.in_width, blk.z_proj.in_channels - blk.z_dim
+    first = i == 0 or dec.blocks[i - 1].res != blk.res
+    # (the segments of _decode: cat[h, pa, acts] and [z] or cat[z, pa])
+    return fwd_pair_expected(eng, _lib, B, blk.res, first, desc(blk.posterior, [w, ctx, w] if ctx else [w, w]),
+                             desc(blk.prior, [w, ctx] if blk.cond_prior and ctx else [w]))
+
+
+def _fwd_pair_cached(eng, dec, i, B):
+    """fwd_pair_layer, asked once per (layer, batch) of an engine (one engine serves one model)"""
+    ok = eng._fwd_pair_ok.get((i, B))
+    if ok is None:
+        ok = eng._fwd_pair_ok[(i, B)] = fwd_pair_layer(eng, dec, i, B)
+    return ok
 
 
 def run_block(eng, blk, segs):
@@ -712,6 +740,12 @@ class HVAE(nn.Module):
             for p_ in dec.bias:  # (lazily built NHWC images: build them before any side-stream section needs one)
                 eng.param_nhwc(p_)
         side_ahead = False
+        # a pass that pairs any layer forks nowhere (Engine.blk3_fwd_pair_serial): the layers the pair does not serve run their prior
+        # Block in line, prior first, as with CGEN_FWD_BRANCH=0
+        serial = (acts is not None and rec2 and eng.prof is None and eng.blk3_fwd_pair_serial
+                  and any(_fwd_pair_cached(eng, dec, j, B) for j in range(len(dec.blocks))))
+        if serial:
+            pipeline = False
         for i, blk in enumerate(dec.blocks):
             res = blk.res
             pa = parents.crop(res)
@@ -732,16 +766,34 @@ class HVAE(nn.Module):
             run_prior = lambda: self._run_block(eng, blk.prior, [p_in, pa_sto] if blk.cond_prior else [p_in])
             # the prior and the posterior Block of a layer are independent: two streams (one fork / join per layer)
             want_two = blk.stochastic and acts is not None and rec2
+            # ... or ONE launch on the main stream (cgen_block3_pair, forward): no fork, no join -- the two queue hops cost the main
+            # chain ~11 us of idle device per layer under graph replay (LABNOTES 32).  The posterior Block's launch is held in the
+            # engine's forward pair slot and goes out with the prior Block's; singly, in this order, if the kernel declines after all
+            paired = want_two and not side_ahead and eng.prof is None and _fwd_pair_cached(eng, dec, i, B)
+            if serial and not paired:
+                want_two = False
             # (a fresh fork: the posterior Block -- the main chain -- is enqueued first, the prior Block behind the mark: Engine.fork_mark)
-            mark = eng.fork_mark() if want_two and not side_ahead else None
+            mark = eng.fork_mark() if want_two and not side_ahead and not paired else None
             t_q0 = len(eng.tape)
-            qout = self._run_block(eng, blk.posterior, [h, pa, acts[res]]) if mark is not None else None
-            t_q1 = len(eng.tape)
-            two = want_two and (side_ahead or eng.fork_side(after=mark))
-            if side_ahead and not two:
-                eng.join_side()
-                side_ahead = False
-            pout = eng.on_side(run_prior, bw=1) if two else run_prior()
+            if paired:
+                try:
+                    eng._blk3f.arm()
+                    qout = self._run_block(eng, blk.posterior, [h, pa, acts[res]])
+                    t_q1 = len(eng.tape)
+                    pout = eng.side_tagged(run_prior, bw=1)
+                except BaseException:
+                    eng._blk3f.reset()
+                    raise
+                eng._blk3f.flush()  # (nothing is held beyond the layer, whichever way the two Blocks were launched)
+                two = False
+            else:
+                qout = self._run_block(eng, blk.posterior, [h, pa, acts[res]]) if mark is not None else None
+                t_q1 = len(eng.tape)
+                two = want_two and (side_ahead or eng.fork_side(after=mark))
+                if side_ahead and not two:
+                    eng.join_side()
+                    side_ahead = False
+                pout = eng.on_side(run_prior, bw=1) if two else run_prior()
             if t_q1 > t_q0 and eng.recording:
                 # tape order [prior][posterior] whichever was launched first: backward() then enqueues the posterior Block's
                 # backward (main strand) BEFORE the prior Block's (side strand) behind the fork -- the main chain must be the first
@@ -801,7 +853,9 @@ class HVAE(nn.Module):
             z_cur = z
             # the next layer's prior chain (z_feat_proj -> prior Block) on the side stream, forked HERE but enqueued behind z_proj:
             # the main chain must be the first edge out of the fork for a captured graph to keep it on one queue (Engine.fork_mark)
-            ahead = feat and pipeline and two and dec.blocks[i + 1].stochastic and not dec.blocks[i + 1].q_correction
+            # (a layer that pairs uses no side stream, so nothing is forked ahead for it; the layer behind a paired one is forked for as before)
+            ahead = (feat and pipeline and (two or paired) and dec.blocks[i + 1].stochastic and not dec.blocks[i + 1].q_correction
+                     and not _fwd_pair_cached(eng, dec, i + 1, B))
             mark = eng.fork_mark() if ahead and eng.fwd_mainfirst else None
             if tail is not None:
                 # the one launch is done, on the main stream: the fork for the next layer's prior chain (upsample -> prior Block) sits

@@ -151,6 +151,15 @@ int cgen_block3(const cgen_block3_args* a, cgen_stream_t stream);
  * guarantees that neither problem reads or accumulates into a tensor the other one writes. */
 int cgen_block3_pair_supported(const cgen_block3_args* a, const cgen_block3_args* b);
 int cgen_block3_pair(const cgen_block3_args* a, const cgen_block3_args* b, cgen_stream_t stream);
+/* The same entry points take two FORWARD problems (pre_act = 1 on both): a decoder layer's posterior Block (a) and prior Block (b),
+ * which today run on two queues.  The two may plan to different kernel instances; the launch runs instance A on the first `na`
+ * workgroups and instance B on the rest, each the body of the single launch on its record, so the results have the single launches'
+ * bits.  Declined (0, nothing launched): one record pre_act and the other not; different image size or batch; different bottleneck
+ * width; a streaming or row-streaming instance, remainder planes or a residual on either record; a combination of instances that
+ * is not compiled (csrc/block.hip, b3_fwd_pair_served).
+ * cgen_block3_pair_plan: what _supported answers, and when that is 1 the plan in out[0 .. 7] = bottleneck / 8, small-image instance
+ * (0 / 1), then per record the phase-B wave split, the tile rows and the workgroups.  Host code: no GPU needed. */
+int cgen_block3_pair_plan(const cgen_block3_args* a, const cgen_block3_args* b, int32_t* out);
 
 /* ------------------------------------------------------------------ fused DEFAULT Block (csrc/block4.hip; binary16)
  * Block.forward of the non-"light" version (vae.py:57-71, 73-84: GELU -> 1x1 -> GELU -> 3x3 -> GELU -> 3x3 -> GELU -> 1x1) as ONE launch,
