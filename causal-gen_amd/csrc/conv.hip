@@ -975,7 +975,9 @@ static bool launch_conv_smallp(const ConvP& p, hipStream_t st) {
   return true;
 }
 
+static thread_local const char* g_last_kernel = "";  // the arm that served this thread's last call (cgen_conv2d_last_kernel)
 static void conv_trace(const ConvP& p, const char* which) {  // CGEN_CONV_TRACE=1: which kernel served which shape
+  g_last_kernel = which;
   static const bool on = getenv("CGEN_CONV_TRACE") != nullptr;
   if (on) fprintf(stderr, "conv %-5s ks%d ci8 %-4d co %-4d res %-3d nseg %d act %d aux %d res %d%d\n", which, p.KS, p.ctot8, p.Co, p.H, p.nseg, p.act,
                   p.aux.p != nullptr, p.res1.p != nullptr, p.res2.p != nullptr);
@@ -1761,6 +1763,8 @@ extern "C" int cgen_conv2d(const cgen_conv_args* a, cgen_stream_t stream) {
   if (rc != CGEN_OK) return rc;
   return a->dtype != CGEN_F16 ? launch_conv<float>(p, (hipStream_t)stream) : launch_conv<h16_t>(p, (hipStream_t)stream);
 }
+
+extern "C" const char* cgen_conv2d_last_kernel(void) { return g_last_kernel; }
 
 // ---- pair launch of two small-image convs (conv_smallp_pair_kernel)
 static bool smallp_pair_fill(const cgen_conv_args* a, SpArgs& s) {

@@ -87,6 +87,9 @@ typedef struct cgen_conv_args {
   int64_t out_rem, res1_rem;
 } cgen_conv_args;
 int cgen_conv2d(const cgen_conv_args* a, cgen_stream_t stream);
+/* Which kernel served the calling thread's last cgen_conv2d / cgen_conv2d_pair: "gen", "tile", "px", "ws", "smlp" or "smlp2" (the pair
+ * launch); "" before any call.  For tests that pin the dispatch; the string is static. */
+const char* cgen_conv2d_last_kernel(void);
 /* Two independent convolutions in ONE launch where both are small-image problems of the same kernel instance (f16, 1x1 or 3x3, the
  * <= ~6000-pixel batches of the <= 12x12 layers: conv_smallp, whose launches are latency-bound whatever their size).  In the reference's
  * graph: the data gradients of the posterior and the prior Block's convs of a DecoderBlock (vae.py:240-301), which autograd runs back to

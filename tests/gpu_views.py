@@ -63,6 +63,28 @@ class Arena:
             self.outs.append((parent, v, parent.clone()))
         return v
 
+    def place(self, pshape, off, shape, values=None, out=False, zero_to=0, planes=1):
+        """`planes` views of `shape` (n, h, w, c) at channel `off` of as many parents of `pshape`, one allocation, every parent filled
+        with NaN: whatever a kernel takes from outside an input view shows in its result, and what it writes outside an output view
+        shows in check_untouched.  `values`: one tensor per plane (any dtype; None leaves that view NaN).  Channels [c, zero_to) of the
+        view's pixels hold zeros, as cgen_view.cpad promises.  Returns the views; the second one starts pn * sn elements after the first."""
+        pn, ph, pw, pc = pshape
+        n, h, w, c = shape
+        whole = torch.full((planes * pn, ph, pw, pc), float("nan"), dtype=self.tdt, device="cuda")
+        assert whole.data_ptr() % 256 == 0
+        views = []
+        for k in range(planes):
+            parent = whole[k * pn:(k + 1) * pn]
+            if zero_to > c:
+                parent[:n, :h, :w, off + c:off + zero_to] = 0
+            v = parent[:n, :h, :w, off:off + c]
+            if values is not None and values[k] is not None:
+                v.copy_(values[k].to(self.tdt))
+            if out:
+                self.outs.append((parent, v, parent.clone()))
+            views.append(v)
+        return views
+
     def flat_out(self, count, init):
         """A contiguous f32 destination with 64 sentinel floats after it."""
         buf = torch.full((count + 64,), float("nan"), device="cuda")
@@ -71,16 +93,19 @@ class Arena:
         self.outs.append((buf, buf[:count], buf.clone()))
         return buf[:count]
 
-    def check_untouched(self, written=None):
-        """Everything outside the written region of every output parent is bit-identical to what it was."""
-        for parent, v, before in self.outs:
+    def check_untouched(self, written=None, cpad=0):
+        """Everything outside the written region of every output parent is bit-identical to what it was (the region: the view, or
+        `written`; `cpad` channels of it where the call also writes the zero padding [c, cpad) of an output view -- one number for
+        every output, or one per output in the order they were made)."""
+        for i, (parent, v, before) in enumerate(self.outs):
+            cp = cpad[i] if isinstance(cpad, (list, tuple)) else cpad
             keep = torch.ones(parent.shape, dtype=torch.bool, device="cuda")
             if parent.dim() == 1:
                 keep[:v.numel()] = False
             else:
                 r = written if written is not None else v
                 c0 = (r.data_ptr() - parent.data_ptr()) // parent.element_size() % parent.stride(2)
-                keep[:r.shape[0], :r.shape[1], :r.shape[2], c0:c0 + r.shape[3]] = False
+                keep[:r.shape[0], :r.shape[1], :r.shape[2], c0:c0 + max(r.shape[3], cp)] = False
             assert torch.equal(_bits(parent)[keep], _bits(before)[keep]), "a write outside the output view"
 
 

@@ -55,6 +55,8 @@ def test_pure_queries_and_arg_validation_without_gpu():
     lib = _lib.load()
     assert lib.reparam_kl_chunks(96, 96, 16) == 72
     assert lib.like_chunks(192, 192) == 36
+    last = lib.conv2d_last_kernel()  # "" until a conv has been launched in this thread (a CPU-only host cannot launch one)
+    assert last in (b"", b"gen", b"tile", b"px", b"ws", b"smlp", b"smlp2")
     import ctypes
 
     w = _lib.WgradArgs()
@@ -79,6 +81,7 @@ def test_pure_queries_and_arg_validation_without_gpu():
         raise AssertionError("expected CgenError")
     except _lib.CgenError as e:
         assert "dtype" in str(e)
+    assert lib.conv2d_last_kernel() == last  # (a call that is refused serves nothing)
 
 
 def ctypes_byref(x):
