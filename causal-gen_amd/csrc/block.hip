@@ -1776,40 +1776,6 @@ static B3Launch b3_plan(B3P& p, const int co_tiles = 0) {  // co_tiles: tiles of
   return L;
 }
 
-template <bool PRE, int NB, int NPG, int SM, int TH, bool REM>
-static void b3_launch_rem(const B3P& p, const B3Launch& L, hipStream_t st) {
-  // (per call: the attribute is per device and per function, the call is a few hundred ns and thread-safe; a `static bool once` was neither)
-  (void)hipFuncSetAttribute((const void*)blk3_kernel<PRE, NB, NPG, SM, TH, REM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL((blk3_kernel<PRE, NB, NPG, SM, TH, REM>), dim3(L.grid), dim3(256), L.lds, st, p);
-}
-template <bool PRE, int NB, int NPG, int SM, int TH = 8>
-static void b3_launch_inst(const B3P& p, const B3Launch& L, hipStream_t st) {
-  if constexpr (PRE && SM == 0) {  // remainder planes of a residual trunk: forward, any-chunk instances (b3_fill / b3_plan see to that)
-    if (p.o[0].out_rem || p.o[0].res_rem) return b3_launch_rem<PRE, NB, NPG, SM, TH, true>(p, L, st);
-  }
-  b3_launch_rem<PRE, NB, NPG, SM, TH, false>(p, L, st);
-}
-template <bool PRE, int NB>
-static void b3_launch_nb(const B3P& p, const B3Launch& L, hipStream_t st) {
-  if constexpr (NB <= 2) {  // streaming instances: a tile is one or two chunks, one output, the wave's pair is fixed
-    if (L.sm == 1 && L.npg == 1) return b3_launch_inst<PRE, NB, 1, 1>(p, L, st);
-    if (L.sm == 1 && L.npg == 2) return b3_launch_inst<PRE, NB, 2, 1>(p, L, st);
-  }
-  if (L.npg == 1) b3_launch_inst<PRE, NB, 1, 0>(p, L, st);
-  else if (L.npg == 2) b3_launch_inst<PRE, NB, 2, 0>(p, L, st);
-  else if (NB <= 3 && L.th == 12) { if constexpr (NB <= 3) b3_launch_inst<PRE, NB, 4, 0, 12>(p, L, st); }
-  else b3_launch_inst<PRE, NB, 4, 0>(p, L, st);
-}
-template <bool PRE>
-static void b3_launch_pre(const B3P& p, const B3Launch& L, hipStream_t st) {
-  switch (p.b / 8) {
-    case 1: b3_launch_nb<PRE, 1>(p, L, st); break;
-    case 2: b3_launch_nb<PRE, 2>(p, L, st); break;
-    case 3: b3_launch_nb<PRE, 3>(p, L, st); break;
-    default: b3_launch_nb<PRE, 4>(p, L, st); break;
-  }
-}
-
 // pair launch: the data-gradient instances without the streaming mode (both problems must plan to the SAME one)
 template <int NB, int NPG, int TH = 8>
 static void b3_pair_inst(const B3P& pa, const B3P& pb, const B3Launch& La, const B3Launch& Lb, hipStream_t st) {
@@ -1875,6 +1841,103 @@ template __global__ void blk3r_kernel<false, 3, 2, 0, true, 1>(B3P);  // its dat
 template __global__ void blk3r_kernel<false, 3, 2, 2, true, 1>(B3P);
 #endif
 
+// ----------------------------------------------------------------------------- single launch: one plan, two entry points
+// The instance a problem launches on and its launch record.  b3_single_plan is the ONLY place that decides; cgen_block3 launches from
+// the record, cgen_block3_plan reports it.  kind 0: blk3_kernel<PRE, NB, NPG, SM, TH, REM> (t[0 .. 4]); 1: blk3s_kernel<PRE>;
+// 2: blk3r_kernel<PRE, NCH, NB, RES, PROJ, NR> (t[0 .. 4], NR = 1: no two-round instance is served).
+struct B3Inst { int kind, pre, t[5]; };
+
+static int b3_single_plan(const cgen_block3_args* a, B3P& p, B3Launch& L, B3Inst& I) {
+  const int sup = b3_fill(a, p);
+  if (!sup) return 0;
+  memset(&I, 0, sizeof(I));
+  L.npg = L.sm = L.th = 0;
+  I.pre = a->pre_act != 0;
+  if (p.rows) {
+    const int nch = a->seg[0].c / 32, nb = p.b / 8;
+    I.kind = 2;
+    I.t[0] = nch; I.t[1] = nb;
+    I.t[2] = !a->o[0].res1.p ? 0 : (p.r_res_tile ? 1 : 2);  // residual: none, from the input ring, from memory
+    I.t[3] = p.wP ? 1 : 0; I.t[4] = 1;
+    L.grid = p.ntiles;
+    L.lds = b3r_lds(nch, nb) + (p.wP ? (size_t)B3R_NW * B3R_PJTB : 0) + (p.r_pool ? b3r_exb(p.o[0].Co) : 0);
+    return sup;
+  }
+  if (p.small) {
+    I.kind = 1;
+    L.grid = p.ntiles;
+    L.lds = b3s_lds(p);
+    return sup;
+  }
+  L = b3_plan(p);
+  I.kind = 0;
+  I.t[0] = p.b / 8 < 4 ? p.b / 8 : 4; I.t[1] = L.npg; I.t[2] = L.sm; I.t[3] = L.th;
+  I.t[4] = (I.pre && L.sm == 0 && (p.o[0].out_rem || p.o[0].res_rem)) ? 1 : 0;  // remainder planes: forward, any-chunk instances (b3_fill / b3_plan see to that)
+  return sup;
+}
+
+template <bool PRE, int NB, int NPG, int SM, int TH, bool REM>
+static void b3_launch_rem(const B3P& p, const B3Launch& L, hipStream_t st) {
+  // (per call: the attribute is per device and per function, the call is a few hundred ns and thread-safe; a `static bool once` was neither)
+  (void)hipFuncSetAttribute((const void*)blk3_kernel<PRE, NB, NPG, SM, TH, REM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL((blk3_kernel<PRE, NB, NPG, SM, TH, REM>), dim3(L.grid), dim3(256), L.lds, st, p);
+}
+template <bool PRE, int NB, int NPG, int SM, int TH = 8>
+static void b3_launch_inst(const B3P& p, const B3Launch& L, const B3Inst& I, hipStream_t st) {
+  if constexpr (PRE && SM == 0) {
+    if (I.t[4]) return b3_launch_rem<PRE, NB, NPG, SM, TH, true>(p, L, st);
+  }
+  b3_launch_rem<PRE, NB, NPG, SM, TH, false>(p, L, st);
+}
+template <bool PRE, int NB>
+static void b3_launch_nb(const B3P& p, const B3Launch& L, const B3Inst& I, hipStream_t st) {
+  const int npg = I.t[1], sm = I.t[2], th = I.t[3];
+  if constexpr (NB <= 2) {  // streaming instances: a tile is one or two chunks, one output, the wave's pair is fixed
+    if (sm == 1 && npg == 1) return b3_launch_inst<PRE, NB, 1, 1>(p, L, I, st);
+    if (sm == 1 && npg == 2) return b3_launch_inst<PRE, NB, 2, 1>(p, L, I, st);
+  }
+  if (npg == 1) b3_launch_inst<PRE, NB, 1, 0>(p, L, I, st);
+  else if (npg == 2) b3_launch_inst<PRE, NB, 2, 0>(p, L, I, st);
+  else if (NB <= 3 && th == 12) { if constexpr (NB <= 3) b3_launch_inst<PRE, NB, 4, 0, 12>(p, L, I, st); }
+  else b3_launch_inst<PRE, NB, 4, 0>(p, L, I, st);
+}
+template <bool PRE>
+static void b3_launch_pre(const B3P& p, const B3Launch& L, const B3Inst& I, hipStream_t st) {
+  switch (I.t[0]) {
+    case 1: b3_launch_nb<PRE, 1>(p, L, I, st); break;
+    case 2: b3_launch_nb<PRE, 2>(p, L, I, st); break;
+    case 3: b3_launch_nb<PRE, 3>(p, L, I, st); break;
+    default: b3_launch_nb<PRE, 4>(p, L, I, st); break;
+  }
+}
+
+template <bool PRE, int NCH, int NB, int RES, bool PROJ>
+static void b3r_launch_inst(const B3P& p, const B3Launch& L, hipStream_t st) {
+  (void)hipFuncSetAttribute((const void*)blk3r_kernel<PRE, NCH, NB, RES, PROJ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL((blk3r_kernel<PRE, NCH, NB, RES, PROJ>), dim3(L.grid), dim3(64 * B3R_NW), L.lds, st, p);
+}
+// the residual modes that exist: forward 0 / 1 / 2 (1: read from the input ring), data gradient 0 / 2, the down Block's forward 0
+template <int NCH, int NB>
+static void b3r_launch_nb(const B3P& p, const B3Launch& L, const B3Inst& I, hipStream_t st) {
+  const int res = I.t[2];
+  if (I.t[3]) {  // the down Block
+    if (I.pre) b3r_launch_inst<true, NCH, NB, 0, true>(p, L, st);
+    else if (res == 0) b3r_launch_inst<false, NCH, NB, 0, true>(p, L, st);
+    else b3r_launch_inst<false, NCH, NB, 2, true>(p, L, st);
+  } else if (I.pre) {
+    if (res == 0) b3r_launch_inst<true, NCH, NB, 0, false>(p, L, st);
+    else if (res == 1) b3r_launch_inst<true, NCH, NB, 1, false>(p, L, st);
+    else b3r_launch_inst<true, NCH, NB, 2, false>(p, L, st);
+  } else {
+    if (res == 0) b3r_launch_inst<false, NCH, NB, 0, false>(p, L, st);
+    else b3r_launch_inst<false, NCH, NB, 2, false>(p, L, st);
+  }
+}
+static void b3r_launch(const B3P& p, const B3Launch& L, const B3Inst& I, hipStream_t st) {
+  if (I.t[0] == 1) { if (I.t[1] == 1) b3r_launch_nb<1, 1>(p, L, I, st); else b3r_launch_nb<1, 2>(p, L, I, st); }
+  else { if (I.t[1] == 1) b3r_launch_nb<2, 1>(p, L, I, st); else b3r_launch_nb<2, 2>(p, L, I, st); }
+}
+
 }  // namespace cgen
 
 using namespace cgen;
@@ -1936,49 +1999,50 @@ extern "C" int cgen_block3_supported(const cgen_block3_args* a) {
   return b3_fill(a, p);
 }
 
+// The plan of the single launch, for tools and tests (host code: the same answer with and without a GPU).  Returns what
+// cgen_block3_supported returns; when that is non-zero, out[0 .. 23] is the record cgen_block3 launches from (include/cgen_hip.h).
+extern "C" int cgen_block3_plan(const cgen_block3_args* a, int32_t* out) {
+  B3P p;
+  B3Launch L;
+  B3Inst I;
+  const int sup = b3_single_plan(a, p, L, I);
+  if (!sup || !out) return sup;
+  for (int i = 0; i < 24; ++i) out[i] = 0;
+  out[0] = I.kind; out[1] = I.pre;
+  if (I.kind != 1) for (int i = 0; i < 5; ++i) out[2 + i] = I.t[i];
+  out[9] = L.grid; out[10] = p.ntiles; out[18] = (int32_t)L.lds;
+  if (I.kind == 0) { out[7] = p.ns; out[8] = p.wb_persist; }
+  if (I.kind == 1) { out[11] = p.s_rows; out[12] = p.s_strips; out[13] = p.s_nmb; }
+  if (I.kind == 2) { out[14] = p.r_rs; out[15] = p.r_sx; out[16] = p.r_sy; out[17] = p.r_res_tile; }
+  return sup;
+}
+
 extern "C" int cgen_block3(const cgen_block3_args* a, cgen_stream_t stream) {
   B3P p;
-  CGEN_REQUIRE(b3_fill(a, p), "cgen_block3: shape / layout not served by the fused Block kernel (ask cgen_block3_supported first)");
+  B3Launch L;
+  B3Inst I;
+  CGEN_REQUIRE(b3_single_plan(a, p, L, I), "cgen_block3: shape / layout not served by the fused Block kernel (ask cgen_block3_supported first)");
   CGEN_REQUIRE((a->pre_act != 0) == (a->mid_aux.p == nullptr), "cgen_block3: pre_act = 1 is the forward pass (no mid_aux), pre_act = 0 the data gradient (mid_aux = the forward mid)");
-  if (p.rows) {
-    const int nch = a->seg[0].c / 32, nb = p.b / 8;
-    const size_t lds = b3r_lds(nch, nb) + (p.wP ? (size_t)B3R_NW * B3R_PJTB : 0) + (p.r_pool ? b3r_exb(p.o[0].Co) : 0);
-#define B3R_LAUNCH(PRE_, NCH_, NB_, RES_, ...) do { (void)hipFuncSetAttribute((const void*)blk3r_kernel<PRE_, NCH_, NB_, RES_, ##__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((blk3r_kernel<PRE_, NCH_, NB_, RES_, ##__VA_ARGS__>), dim3(p.ntiles), dim3(64 * B3R_NW), lds, (hipStream_t)stream, p); } while (0)
-#define B3R_RES(PRE_, NCH_, NB_) do { if (res_mode == 0) B3R_LAUNCH(PRE_, NCH_, NB_, 0); else if (res_mode == 1) B3R_LAUNCH(PRE_, NCH_, NB_, 1); else B3R_LAUNCH(PRE_, NCH_, NB_, 2); } while (0)
-#define B3R_RES_BWD(NCH_, NB_) do { if (res_mode == 0) B3R_LAUNCH(false, NCH_, NB_, 0); else B3R_LAUNCH(false, NCH_, NB_, 2); } while (0)
-    const int res_mode = !a->o[0].res1.p ? 0 : (p.r_res_tile ? 1 : 2);
-#define B3R_DOWN(NCH_, NB_) do { if (a->pre_act) B3R_LAUNCH(true, NCH_, NB_, 0, true); else if (res_mode == 0) B3R_LAUNCH(false, NCH_, NB_, 0, true); else B3R_LAUNCH(false, NCH_, NB_, 2, true); } while (0)
-    if (p.wP) {  // the down Block
-      if (nch == 1) { if (nb == 1) B3R_DOWN(1, 1); else B3R_DOWN(1, 2); } else { if (nb == 1) B3R_DOWN(2, 1); else B3R_DOWN(2, 2); }
-    } else if (a->pre_act) { if (nch == 1) { if (nb == 1) B3R_RES(true, 1, 1); else B3R_RES(true, 1, 2); } else { if (nb == 1) B3R_RES(true, 2, 1); else B3R_RES(true, 2, 2); } }
-    else { if (nch == 1) { if (nb == 1) B3R_RES_BWD(1, 1); else B3R_RES_BWD(1, 2); } else { if (nb == 1) B3R_RES_BWD(2, 1); else B3R_RES_BWD(2, 2); } }
-#undef B3R_DOWN
-#undef B3R_RES
-#undef B3R_RES_BWD
-#undef B3R_LAUNCH
-    static const bool trace_r = getenv("CGEN_CONV_TRACE") != nullptr;
-    if (trace_r) fprintf(stderr, "blk3r[%s] %dx%dx%d c %d b %d Co %d | strips %d x %d of %d rows, grid %d, lds %zu, residual from the tile %d\n", a->mid_aux.p ? "bwd" : "fwd", a->n, a->h, a->w,
-                         a->seg[0].c, p.b, p.o[0].Co, p.r_sx, p.r_sy, p.r_rs, p.ntiles, lds, p.r_res_tile);
+  static const bool trace = getenv("CGEN_CONV_TRACE") != nullptr;
+  if (I.kind == 2) {
+    b3r_launch(p, L, I, (hipStream_t)stream);
+    if (trace) fprintf(stderr, "blk3r[%s] %dx%dx%d c %d b %d Co %d | strips %d x %d of %d rows, grid %d, lds %zu, residual from the tile %d\n", a->mid_aux.p ? "bwd" : "fwd", a->n, a->h, a->w,
+                       a->seg[0].c, p.b, p.o[0].Co, p.r_sx, p.r_sy, p.r_rs, p.ntiles, L.lds, p.r_res_tile);
     return check_launch("cgen_block3(rows)");
   }
-  if (p.small) {
-    const size_t lds = b3s_lds(p);
-    if (a->pre_act) {
+  if (I.kind == 1) {
+    if (I.pre) {
       (void)hipFuncSetAttribute((const void*)blk3s_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((blk3s_kernel<true>), dim3(p.ntiles), dim3(64 * B3S_NW), lds, (hipStream_t)stream, p);
+      hipLaunchKernelGGL((blk3s_kernel<true>), dim3(L.grid), dim3(64 * B3S_NW), L.lds, (hipStream_t)stream, p);
     } else {
       (void)hipFuncSetAttribute((const void*)blk3s_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((blk3s_kernel<false>), dim3(p.ntiles), dim3(64 * B3S_NW), lds, (hipStream_t)stream, p);
+      hipLaunchKernelGGL((blk3s_kernel<false>), dim3(L.grid), dim3(64 * B3S_NW), L.lds, (hipStream_t)stream, p);
     }
-    static const bool trace_s = getenv("CGEN_CONV_TRACE") != nullptr;
-    if (trace_s) fprintf(stderr, "blk3s[%s] %dx%dx%d ctot8 %d b %d Co %d nseg %d nout %d | %d rows per strip, grid %d, lds %zu\n", a->mid_aux.p ? "bwd" : "fwd", a->n, a->h, a->w, p.ctot8, p.b, p.o[0].Co, a->nseg, a->nout, p.s_rows, p.ntiles, lds);
+    if (trace) fprintf(stderr, "blk3s[%s] %dx%dx%d ctot8 %d b %d Co %d nseg %d nout %d | %d rows per strip, grid %d, lds %zu\n", a->mid_aux.p ? "bwd" : "fwd", a->n, a->h, a->w, p.ctot8, p.b, p.o[0].Co, a->nseg, a->nout, p.s_rows, p.ntiles, L.lds);
     return check_launch("cgen_block3(small)");
   }
-  const B3Launch L = b3_plan(p);
-  if (a->pre_act) b3_launch_pre<true>(p, L, (hipStream_t)stream);
-  else b3_launch_pre<false>(p, L, (hipStream_t)stream);
-  static const bool trace = getenv("CGEN_CONV_TRACE") != nullptr;
+  if (I.pre) b3_launch_pre<true>(p, L, I, (hipStream_t)stream);
+  else b3_launch_pre<false>(p, L, I, (hipStream_t)stream);
   if (trace) fprintf(stderr, "blk3[%s] %dx%dx%d ctot8 %d b %d Co %d nseg %d nout %d | ring %d slots, lds %zu, grid %d, persist wb %d, tile rows %d\n", a->mid_aux.p ? "bwd" : "fwd", a->n, a->h, a->w, p.ctot8, p.b, p.o[0].Co, a->nseg, a->nout, p.ns, L.lds, L.grid, p.wb_persist, L.th);
   return check_launch("cgen_block3");
 }

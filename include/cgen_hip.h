@@ -147,6 +147,15 @@ typedef struct cgen_block3_args {
 } cgen_block3_args;
 int cgen_block3_supported(const cgen_block3_args* a);
 int cgen_block3(const cgen_block3_args* a, cgen_stream_t stream);
+/* The plan of the single launch (additive in ABI 411: a new symbol).  Host code: no GPU needed.  Returns what cgen_block3_supported
+ * returns; when that is non-zero and out != NULL, out[0 .. 23] is the record cgen_block3 launches from (entries not named are 0):
+ *   [0] kind: 0 = tile kernel blk3_kernel<PRE, NB, NPG, SM, TH, REM>, 1 = small-image kernel blk3s_kernel<PRE>,
+ *             2 = row-streaming kernel blk3r_kernel<PRE, NCH, NB, RES, PROJ, NR>
+ *   [1] PRE   [2 .. 6] the template arguments after PRE: tile NB, NPG, SM, TH, REM; rows NCH, NB, RES, PROJ, NR; small: none
+ *   [7] ring slots ns, [8] wb_persist (tile)   [9] workgroups   [10] tiles / strips of the launch
+ *   [11] s_rows, [12] s_strips, [13] s_nmb (small)   [14] r_rs, [15] r_sx, [16] r_sy, [17] r_res_tile (rows)   [18] LDS bytes */
+#define CGEN_BLOCK3_PLAN_INTS 24
+int cgen_block3_plan(const cgen_block3_args* a, int32_t* out);
 /* Two independent DATA-GRADIENT problems (pre_act = 0) in ONE launch: the backward of a decoder layer's posterior and prior Blocks
  * (vae.py:240-301: both hang off the layer's reparameterisation, neither reads what the other writes).  Each is 100-400 workgroups on
  * 512 resident slots; one launch runs them side by side without a second queue.  Served when both plan to the same kernel instance

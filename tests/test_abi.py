@@ -73,6 +73,17 @@ def test_pure_queries_and_arg_validation_without_gpu():
     assert lib.conv2d_wgrad_plan(ctypes.byref(w), ctypes.byref(tiled)) >= 1 and tiled.value == 2
     w.dtype = 0  # f32: the generic kernel
     assert lib.conv2d_wgrad_plan(ctypes.byref(w), ctypes.byref(tiled)) >= 1 and tiled.value == 0
+    # cgen_block3_plan is host code: what cgen_block3_supported answers, and the record the launch is made from
+    blk = _lib.Block3Args()
+    blk.dtype, blk.n, blk.h, blk.w, blk.nseg, blk.nout, blk.pre_act = _lib.F16, 2, 24, 24, 1, 1, 1
+    blk.seg[0] = _lib.View(1 << 20, 24 * 24 * 128, 24 * 128, 128, 128, 0)
+    blk.w_a, blk.mid = 1 << 20, _lib.View(1 << 20, 24 * 24 * 32, 24 * 32, 32, 32, 0)
+    blk.o[0].w, blk.o[0].out = 1 << 20, _lib.View(1 << 20, 24 * 24 * 160, 24 * 160, 160, 160, 0)
+    rec = (ctypes.c_int32 * 24)(*([-1] * 24))
+    assert lib.block3_plan(ctypes.byref(blk), rec) == lib.block3_supported(ctypes.byref(blk)) == 1
+    assert tuple(rec[:7]) == (0, 1, 4, 4, 0, 8, 0) and (rec[7], rec[9], rec[10]) == (3, 12, 12) and not any(rec[19:])  # blk3_kernel<true, 4, 4, 0, 8, false>
+    blk.h = 3
+    assert lib.block3_plan(ctypes.byref(blk), rec) == 0 and lib.block3_plan(ctypes.byref(blk), None) == 0 and rec[0] == 0  # (declined: out[] untouched)
     # argument validation happens before any launch, so it is testable on a CPU-only host
     a = _lib.ConvArgs()
     a.dtype = 7
