@@ -544,32 +544,44 @@ static int b4_fill(const cgen_block4_args* a, B4P& p, int& nb8) {
   return 1;
 }
 
-template <bool FWD, int NB8>
-static void b4_launch(const B4P& p, hipStream_t st) {
-  constexpr int PS = (2 * ((NB8 + 1) / 2) + 1) * 16;
-  const size_t lds = (size_t)(B4_N0 + B4_N1 + B4_N2) * PS + B4_BIAS_BYTES + B4_LUT_BYTES;
+// The launch decision, made ONCE per call: cgen_block4 launches from this record and cgen_block4_plan reports it.
+struct B4Plan { int fwd, nb8, nw, grid, lds; };
+static int b4_lds_bytes(const int nb8) {
+  const int ps = (2 * ((nb8 + 1) / 2) + 1) * 16;
+  return (B4_N0 + B4_N1 + B4_N2) * ps + B4_BIAS_BYTES + B4_LUT_BYTES;
+}
+static int b4_plan(const cgen_block4_args* a, B4P& p, B4Plan& pl) {
+  int nb8 = 0;
+  if (!b4_fill(a, p, nb8)) return 0;
   static const int nw_env = [] { const char* e = getenv("CGEN_BLK4_NW"); return e ? atoi(e) : 0; }();  // (4 / 8: force; measurements only)
   // (the data gradient runs next to the background weight-gradient kernel: an eight-wave workgroup has to find eight free wave slots on
   //  one CU at once and waits for that kernel's workgroups to retire -- mimic224 22.4 -> 24.7 ms/step with eight waves there)
-  const bool eight = nw_env == 84 ? FWD && p.ntiles <= 1024 : (nw_env ? nw_env == 8 : FWD && p.ntiles <= 1024);
-  if (eight) {
+  const bool fwd = a->fwd != 0;
+  const bool eight = nw_env == 84 ? fwd && p.ntiles <= 1024 : (nw_env ? nw_env == 8 : fwd && p.ntiles <= 1024);
+  pl.fwd = fwd; pl.nb8 = nb8 == 7 ? 8 : nb8; pl.nw = eight ? 8 : 4; pl.grid = p.ntiles; pl.lds = b4_lds_bytes(pl.nb8);
+  return 1;
+}
+
+template <bool FWD, int NB8>
+static void b4_launch(const B4P& p, const B4Plan& pl, hipStream_t st) {
+  if (pl.nw == 8) {
     (void)hipFuncSetAttribute((const void*)blk4_kernel<FWD, NB8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((blk4_kernel<FWD, NB8, 8>), dim3(p.ntiles), dim3(512), lds, st, p);
+    hipLaunchKernelGGL((blk4_kernel<FWD, NB8, 8>), dim3(pl.grid), dim3(512), (size_t)pl.lds, st, p);
   } else {
     (void)hipFuncSetAttribute((const void*)blk4_kernel<FWD, NB8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((blk4_kernel<FWD, NB8, 4>), dim3(p.ntiles), dim3(256), lds, st, p);
+    hipLaunchKernelGGL((blk4_kernel<FWD, NB8, 4>), dim3(pl.grid), dim3(256), (size_t)pl.lds, st, p);
   }
 }
 template <bool FWD>
-static void b4_launch_dir(const B4P& p, const int nb8, hipStream_t st) {
-  switch (nb8) {
-    case 1: b4_launch<FWD, 1>(p, st); break;
-    case 2: b4_launch<FWD, 2>(p, st); break;
-    case 3: b4_launch<FWD, 3>(p, st); break;
-    case 4: b4_launch<FWD, 4>(p, st); break;
-    case 5: b4_launch<FWD, 5>(p, st); break;
-    case 6: b4_launch<FWD, 6>(p, st); break;
-    default: b4_launch<FWD, 8>(p, st); break;  // (56 / 64 channels: the image pads 56 to 64)
+static void b4_launch_dir(const B4P& p, const B4Plan& pl, hipStream_t st) {
+  switch (pl.nb8) {
+    case 1: b4_launch<FWD, 1>(p, pl, st); break;
+    case 2: b4_launch<FWD, 2>(p, pl, st); break;
+    case 3: b4_launch<FWD, 3>(p, pl, st); break;
+    case 4: b4_launch<FWD, 4>(p, pl, st); break;
+    case 5: b4_launch<FWD, 5>(p, pl, st); break;
+    case 6: b4_launch<FWD, 6>(p, pl, st); break;
+    default: b4_launch<FWD, 8>(p, pl, st); break;  // (57 .. 64 channels)
   }
 }
 
@@ -582,11 +594,21 @@ extern "C" int cgen_block4_supported(const cgen_block4_args* a) {
   int nb8;
   return b4_fill(a, p, nb8);
 }
+extern "C" int cgen_block4_plan(const cgen_block4_args* a, int32_t* out) {
+  B4P p;
+  B4Plan pl;
+  if (!b4_plan(a, p, pl)) return 0;
+  if (out) {
+    for (int i = 0; i < CGEN_BLOCK4_PLAN_INTS; ++i) out[i] = 0;
+    out[0] = pl.fwd; out[1] = pl.nb8; out[2] = pl.nw; out[3] = p.ntiles; out[4] = pl.grid; out[5] = pl.lds;
+    out[6] = p.xcd_order; out[7] = p.tiles_x; out[8] = p.tiles_y; out[9] = p.nch0;
+  }
+  return 1;
+}
 
 template <int NB8>
 static void b4_launch_pair(const B4P& pa, const B4P& pb, hipStream_t st) {
-  constexpr int PS = (2 * ((NB8 + 1) / 2) + 1) * 16;
-  const size_t lds = (size_t)(B4_N0 + B4_N1 + B4_N2) * PS + B4_BIAS_BYTES + B4_LUT_BYTES;
+  const size_t lds = (size_t)b4_lds_bytes(NB8);
   (void)hipFuncSetAttribute((const void*)blk4_pair_kernel<NB8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   hipLaunchKernelGGL((blk4_pair_kernel<NB8>), dim3(pa.ntiles + pb.ntiles), dim3(256), lds, st, pa, pb, pa.ntiles);
 }
@@ -600,6 +622,17 @@ extern "C" int cgen_block4_pair_supported(const cgen_block4_args* a, const cgen_
   B4P pa, pb;
   int nb8;
   return b4_pair_fill(a, b, pa, pb, nb8);
+}
+extern "C" int cgen_block4_pair_plan(const cgen_block4_args* a, const cgen_block4_args* b, int32_t* out) {
+  B4P pa, pb;
+  int nb8 = 0;
+  if (!b4_pair_fill(a, b, pa, pb, nb8)) return 0;
+  if (out) {
+    for (int i = 0; i < CGEN_BLOCK4_PLAN_INTS; ++i) out[i] = 0;
+    out[0] = 0; out[1] = nb8 == 7 ? 8 : nb8; out[2] = 4; out[3] = pa.ntiles; out[4] = pa.ntiles + pb.ntiles; out[5] = b4_lds_bytes(out[1]);
+    out[6] = pb.ntiles;
+  }
+  return 1;
 }
 extern "C" int cgen_block4_pair(const cgen_block4_args* a, const cgen_block4_args* b, cgen_stream_t stream) {
   B4P pa, pb;
@@ -619,10 +652,10 @@ extern "C" int cgen_block4_pair(const cgen_block4_args* a, const cgen_block4_arg
 
 extern "C" int cgen_block4(const cgen_block4_args* a, cgen_stream_t stream) {
   B4P p;
-  int nb8 = 0;
-  CGEN_REQUIRE(b4_fill(a, p, nb8), "cgen_block4: shape / layout not served by the fused default-Block kernel (ask cgen_block4_supported first)");
-  if (a->fwd) b4_launch_dir<true>(p, nb8, (hipStream_t)stream);
-  else b4_launch_dir<false>(p, nb8, (hipStream_t)stream);
+  B4Plan pl;
+  CGEN_REQUIRE(b4_plan(a, p, pl), "cgen_block4: shape / layout not served by the fused default-Block kernel (ask cgen_block4_supported first)");
+  if (pl.fwd) b4_launch_dir<true>(p, pl, (hipStream_t)stream);
+  else b4_launch_dir<false>(p, pl, (hipStream_t)stream);
   static const bool trace = getenv("CGEN_CONV_TRACE") != nullptr;
   if (trace) fprintf(stderr, "blk4[%s] %dx%dx%d chunks %d b %d Co %d nseg %d nout %d | grid %d\n", a->fwd ? "fwd" : "bwd", a->n, a->h, a->w, p.nch0, a->b, p.o[0].Co, a->nseg, a->nout, p.ntiles);
   return check_launch("cgen_block4");

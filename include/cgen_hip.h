@@ -207,11 +207,20 @@ typedef struct cgen_block4_args {
 } cgen_block4_args;
 int cgen_block4_supported(const cgen_block4_args* a);
 int cgen_block4(const cgen_block4_args* a, cgen_stream_t stream);
+/* The plan of the launch (additive in ABI 411: a new symbol).  Host code: no GPU needed, nothing is dereferenced.  Returns what
+ * cgen_block4_supported returns; when that is 1 and out != NULL, out[0 .. 15] is the record cgen_block4 launches from (entries not
+ * named are 0):  [0] fwd   [1] NB8 (8-channel groups of the bottleneck: 1 .. 6, or 8 for 57 .. 64 channels)   [2] waves per workgroup
+ * (4 or 8)   [3] tiles   [4] workgroups   [5] LDS bytes   [6] xcd_order   [7] tiles_x   [8] tiles_y   [9] phase-0 chunks (nch0):
+ * the kernel is blk4_kernel<fwd, NB8, waves>.  cgen_block4_pair_plan: what _pair_supported answers, and blk4_pair_kernel<NB8>'s
+ * launch in [1] NB8, [2] = 4, [3] tiles of a, [4] workgroups, [5] LDS bytes, [6] tiles of b. */
+#define CGEN_BLOCK4_PLAN_INTS 16
+int cgen_block4_plan(const cgen_block4_args* a, int32_t* out);
 /* Two independent DATA-GRADIENT problems (fwd = 0) of the same bottleneck class (ceil(b / 8) equal) in ONE launch: the backward of a
  * decoder layer's posterior and prior Blocks (vae.py:240-301).  Bit-identical to two cgen_block4 calls; the caller guarantees that
  * neither problem reads or accumulates into a tensor the other one writes. */
 int cgen_block4_pair_supported(const cgen_block4_args* a, const cgen_block4_args* b);
 int cgen_block4_pair(const cgen_block4_args* a, const cgen_block4_args* b, cgen_stream_t stream);
+int cgen_block4_pair_plan(const cgen_block4_args* a, const cgen_block4_args* b, int32_t* out);
 
 /* Weight gradient (aten::convolution_backward, weight/bias part) as split-K partials:
  *   partial_w[split][Co][KS*KS][Ci_total] (f32), partial_b[split][Co] (f32, may be NULL)

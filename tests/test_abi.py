@@ -84,6 +84,18 @@ def test_pure_queries_and_arg_validation_without_gpu():
     assert tuple(rec[:7]) == (0, 1, 4, 4, 0, 8, 0) and (rec[7], rec[9], rec[10]) == (3, 12, 12) and not any(rec[19:])  # blk3_kernel<true, 4, 4, 0, 8, false>
     blk.h = 3
     assert lib.block3_plan(ctypes.byref(blk), rec) == 0 and lib.block3_plan(ctypes.byref(blk), None) == 0 and rec[0] == 0  # (declined: out[] untouched)
+    # cgen_block4_plan likewise: blk4_kernel<true, 2, 8>, 18 tiles of 8 x 16, four chunks of 32 input channels
+    b4 = _lib.Block4Args()
+    b4.dtype, b4.n, b4.h, b4.w, b4.nseg, b4.nout, b4.fwd, b4.b = _lib.F16, 2, 24, 40, 1, 1, 1, 16
+    b4.seg[0] = _lib.View(1 << 20, 24 * 40 * 128, 40 * 128, 128, 128, 0)
+    for k in range(3):
+        b4.wimg[k], b4.mid[k] = 1 << 20, _lib.View(1 << 20, 24 * 40 * 16, 40 * 16, 16, 16, 0)
+    b4.o[0].w, b4.o[0].out = 1 << 20, _lib.View(1 << 20, 24 * 40 * 64, 40 * 64, 64, 64, 0)
+    rec = (ctypes.c_int32 * 16)(*([-1] * 16))
+    assert lib.block4_plan(ctypes.byref(b4), rec) == lib.block4_supported(ctypes.byref(b4)) == 1
+    assert tuple(rec[:5]) == (1, 2, 8, 18, 18) and tuple(rec[6:10]) == (0, 3, 3, 4) and not any(rec[10:])
+    b4.b = 56
+    assert lib.block4_plan(ctypes.byref(b4), rec) == 0 and lib.block4_plan(ctypes.byref(b4), None) == 0 and rec[0] == 1  # (declined: out[] untouched)
     # argument validation happens before any launch, so it is testable on a CPU-only host
     a = _lib.ConvArgs()
     a.dtype = 7

@@ -101,13 +101,15 @@ def test_entry_points_reject_bad_arguments_before_launch():
 
     lib, L = _lib.load(), _lib
 
-    def all3(recs, n, ncol=4, rows=8, obs=OBS, terms=TERMS, loss=LOSS, coef=COEF, ws=WS, ws_bytes=1 << 40, table_rows=8, query=True):
+    def all3(recs, n, ncol=4, rows=8, obs=OBS, terms=TERMS, loss=LOSS, coef=COEF, ws=WS, ws_bytes=1 << 40, table_rows=8, query=True, fwd=True):
+        """fwd=False: a record that is VALID for cgen_pgm_nll_fwd -- that call would launch on the stand-in addresses where a GPU is present."""
         out = []
         if query:
             rc = lib._raw_cgen_pgm_workspace(recs, n, rows, C.byref(L.i64(0)))
             out.append((rc, lib.last_error().decode()))
-        rc = lib._raw_cgen_pgm_nll_fwd(recs, n, obs, ncol, table_rows, None, rows, terms, loss, None)
-        out.append((rc, lib.last_error().decode()))
+        if fwd:
+            rc = lib._raw_cgen_pgm_nll_fwd(recs, n, obs, ncol, table_rows, None, rows, terms, loss, None)
+            out.append((rc, lib.last_error().decode()))
         rc = lib._raw_cgen_pgm_nll_fwd_bwd(recs, n, obs, ncol, table_rows, None, rows, terms, loss, coef, ws, ws_bytes, None)
         out.append((rc, lib.last_error().decode()))
         return out
@@ -146,10 +148,10 @@ def test_entry_points_reject_bad_arguments_before_launch():
             assert rc < 0 and words in msg, (words, msg)
     one = _recs(good)
     for kw, words in ((dict(coef=None), "null coef_dev"), (dict(ws=None), "null workspace"), (dict(ws_bytes=4 * 1218 - 1), "workspace too small")):
-        rc, msg = all3(one, 1, **kw)[-1]
+        rc, msg = all3(one, 1, fwd=False, **kw)[-1]
         assert rc < 0 and words in msg, (words, msg)
     nog = _mech(L.PGM_AFFINE, nctx=2, ctx_col=[1, 2], nhidden=2, width=[32, 32], g=[P, P, P, P, 0, P])
-    rc, msg = all3(_recs(nog), 1)[-1]
+    rc, msg = all3(_recs(nog), 1, fwd=False)[-1]
     assert rc < 0 and "null gradient pointer g[4]" in msg, msg
 
 
