@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from .pairing import BlockRec, PairSlot, may_pair
+from .latent_tail import LatentTailMixin
 from .wgrad_sched import WgradMixin
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, F16, F32, F32S, NULL_VIEW, UNARY_CLAMP_MIN, UNARY_LEAKY_RELU, View
 
@@ -235,7 +236,7 @@ class ConvSite:
                 self.frag_numel["a16_dg"] = 9 * (self.co // 32) * 512
 
 
-class Engine(WgradMixin):
+class Engine(WgradMixin, LatentTailMixin):
     CHUNK = 1024  # elements per block of the multi-tensor kernels (MT_CHUNK in multitensor.hip)
 
     def __init__(self, device, dtype="f32"):
@@ -345,25 +346,7 @@ class Engine(WgradMixin):
         self.conv_pair = os.environ.get("CGEN_CONV_PAIR", "1") != "0"
         self._conv = PairSlot(self, self._dgrad_single, lambda h, a: self.lib.conv2d_pair(C.byref(h), C.byref(a), self.stream),
                               lambda h, a: self.lib.conv2d_pair_supported(C.byref(h), C.byref(a)))
-        # A stochastic decoder layer's backward latent tail -- the 1x1 data gradients of z_feat_proj and z_proj and the reparam backward,
-        # three adjacent tape entries -- as ONE launch (cgen_latent_tail_bwd; _latent_tail_at / _bw_latent_tail).  0: the four launches.
-        self.lat_tail = os.environ.get("CGEN_LAT_TAIL", "1") != "0"
-        self.lat_tail_minpx = int(os.environ.get("CGEN_LAT_TAIL_MINPX", "0"))  # layers with fewer pixels (n * h * w) keep the four launches
-        # its arithmetic: by default the four launches' own, bit for bit (every GEMM summed and rounded to binary16 where they store
-        # grad(z) / grad(p_feat)); 1: one f32 sum and one rounding per output -- closer to exact, and no longer the same bits
-        self.lat_tail_exact = os.environ.get("CGEN_LAT_TAIL_EXACT", "0") != "0"
-        self.lat_tails = 0  # fused launches of the last backward()
-        # The same layer's FORWARD tail -- reparam + KL, z_proj, z_feat_proj -- as one launch (cgen_latent_tail_fwd; latent_tail_fwd below):
-        # the three launches' bits, the three tape entries.  0: the three launches.
-        self.lat_tail_fwd = os.environ.get("CGEN_LAT_TAIL_FWD", "1") != "0"
-        self.lat_tail_fwd_minpx = int(os.environ.get("CGEN_LAT_TAIL_FWD_MINPX", "0"))  # layers with fewer pixels (n * h * w) keep the three launches
-        self.lat_tails_fwd = 0  # fused forward launches since begin()
-        # The DETERMINISTIC decoder layers (z = p_loc: the layers above z_max_res, the largest tensors of the model) the same way, both
-        # directions (the same two entry points without q_loc / q_ls; latent_tail_det_fwd / _bw_latent_tail_det).  0: z_proj and
-        # z_feat_proj as launches of their own, their data gradients, the residual's copy into grad(p_feat) and the zero fill of grad(p_ls).
-        self.lat_tail_det = os.environ.get("CGEN_LAT_TAIL_DET", "1") != "0"
-        self.lat_tails_det = 0      # fused launches of deterministic layers in the last backward()
-        self.lat_tails_det_fwd = 0  # ... in forward passes since begin()
+        self._init_latent_tail()  # (latent_tail.LatentTailMixin: a decoder layer's latent tail as one launch each way)
         # The discretised-Gaussian likelihood head of a recorded pass -- the 1x1 convs x_loc / x_logscale and the NLL around them -- as
         # one launch each way (cgen_dgauss_head_fwd / _bwd; like_head_fwd / _bw_like_head below): the bits of the three forward and
         # the six backward launches it stands for, ONE tape entry.  0: those launches.
@@ -1282,96 +1265,6 @@ class Engine(WgradMixin):
             self.tape.append((self._bw_reparam, (q_loc, q_ls, p_loc, p_ls, z, logt, None if fb is None else fb[2], self.kl_coef_override)))
         return z
 
-    def latent_tail_fwd(self, site_p, site_f, q_loc, q_ls, p_loc, p_ls, p_feat, h, pa, eps, stream_id, logt, kl_ptr, kl_stride, fb=None,
-                        tape_hold=None):
-        """reparam_kl -> conv(z_proj, [z, pa], res1=h, res2=p_feat, trunk=True) -> conv(z_feat_proj, [z, p_feat]) (`site_f` None: the
-        layer has none) as ONE launch on the current stream, with the three launches' bits and their three tape entries in their
-        places (z_feat_proj's goes to `tape_hold`).  Returns (z, h', zf or None), or None -- nothing done, the caller runs the three
-        launches -- when the kernel does not serve the layer, when per-site timing is on, or under CGEN_ABLATE."""
-        if not self.lat_tail_fwd or self.dt != F16 or self.prof is not None or self._ablate:
-            return None
-        n, hh, ww, zd, c = q_loc.n, q_loc.h, q_loc.w, q_loc.c, site_p.co
-        if n * hh * ww < self.lat_tail_fwd_minpx or h.rem or p_feat.rem or (self.trunk_rem and max(hh, ww) <= self.trunk_maxres):
-            return None
-        if site_p.ks != 1 or list(site_p.seg_c) != [zd, pa.c] or (site_f is not None and (site_f.ks != 1 or list(site_f.seg_c) != [zd, c])):
-            return None
-        t = _lib.LatentTailFwdArgs()
-        t.dtype, t.n, t.h, t.w, t.z_dim, t.c, t.ctx = self.dt, n, hh, ww, zd, c, pa.c
-        t.kl_stride, t.stream_id, t.logt = kl_stride, stream_id, logt
-        t.q_loc, t.q_ls, t.p_loc, t.p_ls, t.p_feat, t.h_in, t.pa = q_loc.cv(), q_ls.cv(), p_loc.cv(), p_ls.cv(), p_feat.cv(), h.cv(), pa.cv()
-        t.eps = eps.cv() if eps is not None else NULL_VIEW
-        # (probe views for _supported(), which looks at shapes, strides and alignment: the layout new() will give the outputs, at a
-        # pointer with the arena's alignment)
-        probe = lambda c_: View(h.base.ptr, hh * ww * c_, ww * c_, c_, c_, 0)
-        t.z, t.h_out, t.zf = probe(zd), probe(c), (NULL_VIEW if site_f is None else probe(site_f.co))
-        t.img_p, t.img_f = site_p.img_fwd, (site_f.img_fwd if site_f is not None else None)
-        bp, bf = site_p.conv.bias, (site_f.conv.bias if site_f is not None else None)
-        t.bias_p, t.bias_f = (bp.data_ptr() if bp is not None else None), (bf.data_ptr() if bf is not None else None)
-        t.rng, t.kl_part = self.rng_ptr(), kl_ptr
-        if not self.lib.latent_tail_fwd_supported(C.byref(t)):
-            return None
-        # ---- committed: the allocations, the launches' bookkeeping and the tape entries of the three calls, in their order
-        z = self.new(n, hh, ww, zd)
-        if fb is not None:
-            self.lib.kl_channel_sums(self.dt, n, hh, ww, zd, q_loc.cv(), q_ls.cv(), p_loc.cv(), p_ls.cv(), logt, fb[0] + 4 * fb[2], fb[1], self.stream)
-            self.launches += 1
-        h2 = self.new(n, hh, ww, c)
-        zf = self.new(n, hh, ww, site_f.co) if site_f is not None else None
-        t.z, t.h_out, t.zf = z.cv(), h2.cv(), (zf.cv() if zf is not None else NULL_VIEW)
-        self.lib.latent_tail_fwd(C.byref(t), self.stream)
-        self.launches += 1
-        self.lat_tails_fwd += 1
-        if self.recording:
-            self.tape.append((self._bw_reparam, (q_loc, q_ls, p_loc, p_ls, z, logt, None if fb is None else fb[2], self.kl_coef_override)))
-            if self._dbg_names is not None:
-                self._dbg_names[id(h2.base)] = site_p.name
-            self.tape.append((self._bw_conv, (site_p, [z, pa], ACT_NONE, h2, h, p_feat), self._bw_tag))
-            if zf is not None:
-                if self._dbg_names is not None:
-                    self._dbg_names[id(zf.base)] = site_f.name
-                (self.tape if tape_hold is None else tape_hold).append((self._bw_conv, (site_f, [z, p_feat], ACT_NONE, zf, None, None), 0))
-        return z, h2, zf
-
-    def latent_tail_det_fwd(self, site_p, site_f, p_loc, p_feat, h, pa, tape_hold=None):
-        """A deterministic layer's tail (z = p_loc): conv(z_proj, [p_loc, pa], res1=h, res2=p_feat, trunk=True) -> conv(z_feat_proj,
-        [p_loc, p_feat]) (`site_f` None: the layer has none) as ONE launch on the current stream, with the two launches' bits and their
-        two tape entries in their places (z_feat_proj's goes to `tape_hold`).  Returns (h', zf or None), or None -- nothing done, the
-        caller runs the two launches -- under the conditions of latent_tail_fwd."""
-        if not self.lat_tail_det or self.dt != F16 or self.prof is not None or self._ablate:
-            return None
-        n, hh, ww, zd, c = p_loc.n, p_loc.h, p_loc.w, p_loc.c, site_p.co
-        if h.rem or p_feat.rem or (self.trunk_rem and max(hh, ww) <= self.trunk_maxres):
-            return None
-        if site_p.ks != 1 or list(site_p.seg_c) != [zd, pa.c] or (site_f is not None and (site_f.ks != 1 or list(site_f.seg_c) != [zd, c])):
-            return None
-        t = _lib.LatentTailFwdArgs()
-        t.dtype, t.n, t.h, t.w, t.z_dim, t.c, t.ctx = self.dt, n, hh, ww, zd, c, pa.c
-        t.p_loc, t.p_feat, t.h_in, t.pa = p_loc.cv(), p_feat.cv(), h.cv(), pa.cv()
-        t.q_loc = t.q_ls = t.p_ls = t.eps = t.z = NULL_VIEW  # (absent q_loc / q_ls: the deterministic form)
-        probe = lambda c_: View(h.base.ptr, hh * ww * c_, ww * c_, c_, c_, 0)  # (see latent_tail_fwd)
-        t.h_out, t.zf = probe(c), (NULL_VIEW if site_f is None else probe(site_f.co))
-        t.img_p, t.img_f = site_p.img_fwd, (site_f.img_fwd if site_f is not None else None)
-        bp, bf = site_p.conv.bias, (site_f.conv.bias if site_f is not None else None)
-        t.bias_p, t.bias_f = (bp.data_ptr() if bp is not None else None), (bf.data_ptr() if bf is not None else None)
-        if not self.lib.latent_tail_fwd_supported(C.byref(t)):
-            return None
-        # ---- committed: the allocations, the launches' bookkeeping and the tape entries of the two calls, in their order
-        h2 = self.new(n, hh, ww, c)
-        zf = self.new(n, hh, ww, site_f.co) if site_f is not None else None
-        t.h_out, t.zf = h2.cv(), (zf.cv() if zf is not None else NULL_VIEW)
-        self.lib.latent_tail_fwd(C.byref(t), self.stream)
-        self.launches += 1
-        self.lat_tails_det_fwd += 1
-        if self.recording:
-            if self._dbg_names is not None:
-                self._dbg_names[id(h2.base)] = site_p.name
-            self.tape.append((self._bw_conv, (site_p, [p_loc, pa], ACT_NONE, h2, h, p_feat), self._bw_tag))
-            if zf is not None:
-                if self._dbg_names is not None:
-                    self._dbg_names[id(zf.base)] = site_f.name
-                (self.tape if tape_hold is None else tape_hold).append((self._bw_conv, (site_f, [p_loc, p_feat], ACT_NONE, zf, None, None), self._bw_tag))
-        return h2, zf
-
     def _like_head_args(self, site_loc, site_ls, h, params, x):
         t = _lib.DgaussHeadArgs()
         t.dtype, t.n, t.h, t.w = self.dt, h.n, h.h, h.w
@@ -1908,162 +1801,6 @@ class Engine(WgradMixin):
         if {id(v.base) for v in g1 if v.rg} & {id(v.base) for v in g3 if v.rg}:  # both would accumulate into one gradient
             return False
         return s0.ks == s2.ks
-
-    def _latent_tail_at(self, i):
-        """tape[i], [i-1], [i-2] = z_feat_proj, z_proj, reparam of one stochastic decoder layer (backward order; a layer without
-        z_feat_proj: tape[i], [i-1] = z_proj, reparam): returns their argument tuples (None for an absent z_feat_proj), else None.
-        Recognised by structure alone: two 1x1 convs without activation that read the reparam's z as their first segment, z_proj adding
-        a channel slice of the prior Block's output (p_feat) as a residual, z_feat_proj reading that same slice as its second segment."""
-        tape = self.tape
-
-        def conv_at(j):
-            if j < 0 or tape[j][0] != self._bw_conv:
-                return None
-            site, segs, act, out, r1, r2 = tape[j][1]
-            return tape[j][1] if site.ks == 1 and act == ACT_NONE and len(segs) == 2 and segs[0].rg and site.seg_rg[0] else None
-
-        a, f = conv_at(i), None
-        if a is None:
-            return None
-        if a[4] is None and a[5] is None:  # no residuals: z_feat_proj, with z_proj behind it
-            a, f, i = conv_at(i - 1), a, i - 1
-            if a is None or f[1][0] is not a[1][0] or not (f[1][1].rg and f[0].seg_rg[1]):
-                return None
-        if i < 1 or tape[i - 1][0] != self._bw_reparam:
-            return self._latent_tail_det(f, a)
-        r = tape[i - 1][1]
-        q_loc, q_ls, p_loc, p_ls, z = r[:5]
-        site, segs, _, out, r1, r2 = a
-        zd = z.c
-        if segs[0] is not z or (segs[1].rg and site.seg_rg[1]) or not all(t.rg for t in (q_loc, q_ls, p_loc, p_ls)):
-            return None
-        pb, qb = p_loc.base, q_loc.base
-        slices = ((q_loc, qb, 0), (q_ls, qb, zd), (p_loc, pb, 0), (p_ls, pb, zd))
-        if pb is qb or any(t.base is not b or t.coff != o or t.c != zd for t, b, o in slices) or qb.c < 2 * zd:
-            return None
-        pf = [t for t in (r1, r2) if t is not None and t.base is pb]  # the residual that is p_feat
-        if len(pf) != 1 or not pf[0].rg or pf[0].coff != 2 * zd or pf[0].c != site.co or pb.c != 2 * zd + site.co:
-            return None
-        if f is not None and (f[1][1].base is not pb or f[1][1].coff != 2 * zd or f[1][1].c != site.co):
-            return None
-        return f, a, r
-
-    def _latent_tail_det(self, f, a):
-        """The deterministic form of the pattern (no reparam entry in front; z = p_loc): z_proj's first segment is the channel slice
-        [0, Z) of the base -- the prior Block's output -- whose slice [2Z, 2Z + C) is its residual, z_feat_proj (if any) reads the same
-        two slices.  Returns (f, a, None), else None."""
-        if not self.lat_tail_det:
-            return None
-        site, segs, _, out, r1, r2 = a
-        z = segs[0]
-        pb, zd = z.base, z.c
-        if z is pb or z.coff != 0 or pb.c != 2 * zd + site.co or (segs[1].rg and site.seg_rg[1]):
-            return None
-        pf = [t for t in (r1, r2) if t is not None and t.base is pb]  # the residual that is p_feat
-        if len(pf) != 1 or not pf[0].rg or pf[0].coff != 2 * zd or pf[0].c != site.co:
-            return None
-        if f is not None and (f[1][1].base is not pb or f[1][1].coff != 2 * zd or f[1][1].c != site.co):
-            return None
-        return f, a, None
-
-    def _bw_latent_tail_det(self, f, a):
-        """The one or two entries _latent_tail_det found as one cgen_latent_tail_bwd launch (its form without q_loc / q_ls): the data
-        gradients into grad(p_loc), grad(p_feat) with the residual's share, and zeros for grad(p_ls), which nobody writes -- the whole
-        2Z + C pixel of the prior Block's output gradient, so no copy is parked as a rider and no fill follows.  Returns False --
-        nothing done -- as _bw_latent_tail does, and when that gradient already holds a value (the kernel does not accumulate)."""
-        site_z, segs_z, _, out_z, r1, r2 = a
-        p_loc = segs_z[0]
-        zd, c = p_loc.c, site_z.co
-        if self._ablate:
-            return False
-        pall = p_loc.base.chan(0, 2 * zd + c)
-        e = self.grads.get(id(p_loc.base))
-        if e is not None and self._missing(e[1], 0, 2 * zd + c) != [(0, 2 * zd + c)]:
-            return False
-        if self._frozen(pall) or id(p_loc.base) in self._riders:
-            return False
-        g_h = self.grad_read(out_z)
-        if g_h is None:
-            return False
-        g_f = self.grad_read(f[3]) if f is not None else None
-        t = _lib.LatentTailArgs()
-        t.dtype, t.n, t.h, t.w, t.z_dim, t.c = self.dt, p_loc.n, p_loc.h, p_loc.w, zd, c
-        t.parity = 0 if self.lat_tail_exact else 1
-        t.g_h = g_h.cv()
-        t.g_f = g_f.cv() if g_f is not None else NULL_VIEW
-        t.gz_in = t.q_loc = t.q_ls = t.p_loc = t.p_ls = t.z = t.out_q = NULL_VIEW  # (absent q_loc / q_ls: the deterministic form)
-        t.out_p = self._gentry(p_loc.base)[0].chan(0, 2 * zd + c).cv()  # (the view grad_write will hand out below)
-        if g_f is not None:
-            t.img_fz, t.img_fp = f[0].img_dg[0], f[0].img_dg[1]
-        t.img_pz = site_z.img_dg[0]
-        if not self.lib.latent_tail_bwd_supported(C.byref(t)):
-            return False
-        # ---- committed: the bookkeeping of the entries, in their order
-        if g_f is not None and self._needs_wgrad(f[0]):
-            self._wgrad(f[0], f[1], ACT_NONE, g_f)
-        for res in (r1, r2):
-            if res is not None and res.rg and res.base is not p_loc.base:  # (p_feat's share of G_h is added by the kernel)
-                self._grad_residual(res, g_h, out_z, segs_z)
-        if self._needs_wgrad(site_z):
-            self._wgrad(site_z, segs_z, ACT_NONE, g_h)
-        gp, acc_p = self.grad_write(pall)
-        assert not acc_p
-        t.out_p = gp.cv()
-        self.lib.latent_tail_bwd(C.byref(t), self.stream)
-        self.launches += 1
-        self.lat_tails_det += 1
-        return True
-
-    def _bw_latent_tail(self, f, a, r):
-        """The three entries _latent_tail_at found as one cgen_latent_tail_bwd launch.  Returns False -- nothing done, the caller runs
-        the four launches -- when the kernel does not serve the shapes or a gradient buffer involved may not be written in place."""
-        if r is None:
-            return self._bw_latent_tail_det(f, a)
-        q_loc, q_ls, p_loc, p_ls, z, logt, fb_col, coef_ptr = r
-        site_z, segs_z, _, out_z, r1, r2 = a
-        zd, c = z.c, site_z.co
-        if self._ablate or z.n * z.h * z.w < self.lat_tail_minpx:
-            return False
-        pall, qall = p_loc.base.chan(0, 2 * zd + c), q_loc.base.chan(0, 2 * zd)
-        if self._frozen(pall) or self._frozen(qall) or id(p_loc.base) in self._riders or id(q_loc.base) in self._riders:
-            return False
-        g_h = self.grad_read(out_z)
-        if g_h is None:
-            return False
-        g_f = self.grad_read(f[3]) if f is not None else None
-        gz_in = self.grad_read(z)
-        t = _lib.LatentTailArgs()
-        t.dtype, t.n, t.h, t.w, t.z_dim, t.c = self.dt, z.n, z.h, z.w, zd, c
-        t.coef_stride, t.logt, t.parity = 0, logt, 0 if self.lat_tail_exact else 1
-        t.g_h = g_h.cv()
-        t.g_f = g_f.cv() if g_f is not None else NULL_VIEW
-        t.gz_in = gz_in.cv() if gz_in is not None else NULL_VIEW
-        t.q_loc, t.q_ls, t.p_loc, t.p_ls, t.z = q_loc.cv(), q_ls.cv(), p_loc.cv(), p_ls.cv(), z.cv()
-        # (the views grad_write will hand out below: _gentry creates the buffers, as the four launches' grad_write would)
-        t.out_p = self._gentry(p_loc.base)[0].chan(0, 2 * zd + c).cv()
-        t.out_q = self._gentry(q_loc.base)[0].chan(0, 2 * zd).cv()
-        if g_f is not None:
-            t.img_fz, t.img_fp = f[0].img_dg[0], f[0].img_dg[1]
-        t.img_pz = site_z.img_dg[0]
-        t.coef = self.kl_coef_ptr if coef_ptr is None else coef_ptr
-        t.chan_scale = None if fb_col is None else self.kl_chan_ptr + 4 * fb_col
-        if not self.lib.latent_tail_bwd_supported(C.byref(t)):
-            return False
-        # ---- committed: the bookkeeping of the three entries, in their order
-        if g_f is not None and self._needs_wgrad(f[0]):
-            self._wgrad(f[0], f[1], ACT_NONE, g_f)
-        for res in (r1, r2):
-            if res is not None and res.rg and res.base is not p_loc.base:  # (p_feat's share of G_h is added by the kernel)
-                self._grad_residual(res, g_h, out_z, segs_z)
-        if self._needs_wgrad(site_z):
-            self._wgrad(site_z, segs_z, ACT_NONE, g_h)
-        gp, acc_p = self.grad_write(pall)
-        gq, acc_q = self.grad_write(qall)
-        t.out_p, t.out_q, t.acc_p, t.acc_q = gp.cv(), gq.cv(), 1 if acc_p else 0, 1 if acc_q else 0
-        self.lib.latent_tail_bwd(C.byref(t), self.stream)
-        self.launches += 1
-        self.lat_tails += 1
-        return True
 
     def _dgrad_target(self, s):
         """Where the data gradient of input tensor `s` goes: (view to write, view to add when accumulating, accumulate?)."""

@@ -803,7 +803,7 @@ class HVAE(nn.Module):
             p_loc, p_ls, p_feat = pout.chan(0, zd), pout.chan(zd, 2 * zd), pout.chan(2 * zd, pout.c)
             feat = not blk.q_correction and i + 1 < len(dec.blocks)
             hold = []
-            tail = None  # (z, h', zf) when the layer's forward tail ran as one launch (Engine.latent_tail_fwd)
+            q_loc = q_ls = eps = kptr = kstride = fbl = None  # (the posterior side: set by a stochastic layer of a training / abduction pass)
             if blk.stochastic:
                 sid += 1
                 if acts is not None:
@@ -817,17 +817,6 @@ class HVAE(nn.Module):
                     kptr = kl[0] + 4 * kl[2][i] if kl is not None else self._scratch_kl(eng, B, res, zd)
                     kstride = kl[1] if kl is not None else _lib.load().reparam_kl_chunks(res, res, zd)
                     fbl = None if fb is None else (fb[0], fb[1], fb[2][i])
-                    # reparam + KL, z_proj and z_feat_proj as ONE launch on the main stream where the kernel serves the layer: the same
-                    # bits, the same three tape entries (z_feat_proj's in `hold`)
-                    tail = eng.latent_tail_fwd(self._site(eng, blk.z_proj), self._site(eng, blk.z_feat_proj) if feat else None, q_loc, q_ls,
-                                               p_loc, p_ls, p_feat, h, pa, eps, sid, logt, kptr, kstride, fb=fbl, tape_hold=hold)
-                    z = tail[0] if tail is not None else eng.reparam_kl(q_loc, q_ls, p_loc, p_ls, eps, sid, logt, kptr, kstride, fb=fbl)
-                    if collect == "z":
-                        out.append(z)
-                    elif collect == "q":
-                        out.append((z, q_loc, q_ls))
-                    elif collect == "qp":  # (standalone Decoder.forward: everything a stats dict needs)
-                        out.append((z, q_loc, q_ls, p_loc, p_ls))
                 else:
                     zi = latents[i] if i < len(latents) else None
                     if zi is not None:
@@ -839,17 +828,20 @@ class HVAE(nn.Module):
                             out.append((p_loc, p_ls))
             else:
                 z = p_loc
-                # z_proj and z_feat_proj as ONE launch where the kernel serves the layer: the same bits, the same two tape entries
-                # (z_feat_proj's in `hold`); no fork is pending here (`two` needs a stochastic layer).  Training and abduction passes, as above.
-                dtail = eng.latent_tail_det_fwd(self._site(eng, blk.z_proj), self._site(eng, blk.z_feat_proj) if feat else None,
-                                                p_loc, p_feat, h, pa, tape_hold=hold) if acts is not None else None
-                if dtail is not None:
-                    t_zp = len(eng.tape)
-                    h = self._run_block(eng, blk.conv, [dtail[0]])
-                    if feat:
-                        z = dtail[1]
-                    eng.tape[t_zp:t_zp] = hold
-                    continue
+            # [reparam + KL,] z_proj and z_feat_proj as ONE launch on the main stream where the kernel serves the layer: the same bits, the
+            # same tape entries (z_feat_proj's in `hold`); q_loc None: a deterministic layer.  Training and abduction passes; (z, h', zf)
+            # when it ran (Engine.latent_tail_fwd)
+            tail = eng.latent_tail_fwd(self._site(eng, blk.z_proj), self._site(eng, blk.z_feat_proj) if feat else None,
+                                       q_loc, q_ls, p_loc, p_ls, p_feat, h, pa, eps, sid, logt, kptr, kstride, fb=fbl,
+                                       tape_hold=hold) if acts is not None else None
+            if q_loc is not None:
+                z = tail[0] if tail is not None else eng.reparam_kl(q_loc, q_ls, p_loc, p_ls, eps, sid, logt, kptr, kstride, fb=fbl)
+                if collect == "z":
+                    out.append(z)
+                elif collect == "q":
+                    out.append((z, q_loc, q_ls))
+                elif collect == "qp":  # (standalone Decoder.forward: everything a stats dict needs)
+                    out.append((z, q_loc, q_ls, p_loc, p_ls))
             z_cur = z
             # the next layer's prior chain (z_feat_proj -> prior Block) on the side stream, forked HERE but enqueued behind z_proj:
             # the main chain must be the first edge out of the fork for a captured graph to keep it on one queue (Engine.fork_mark)
@@ -859,7 +851,9 @@ class HVAE(nn.Module):
             mark = eng.fork_mark() if ahead and eng.fwd_mainfirst else None
             if tail is not None:
                 # the one launch is done, on the main stream: the fork for the next layer's prior chain (upsample -> prior Block) sits
-                # behind it, and the conv Block -- the main chain -- is still the first edge out of it
+                # behind it, and the conv Block -- the main chain -- is still the first edge out of it.  (A deterministic layer forks
+                # nothing: `two` and `paired` need a stochastic layer, so `ahead` is False and `mark` None, and this is "run the conv
+                # Block on h', take zf as the next z, splice `hold` behind z_proj")
                 h = tail[1]
                 t_zp = len(eng.tape)
                 if ahead and mark is None and eng.fork_side():

@@ -25,29 +25,13 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+from latent_tail_cases import _batch, _ceil, _dgrad_image, _lib, _seed, _small_model
+
 Z = 16
 CTX = 4
 SHAPES = [(3, 6, 6, 192), (2, 12, 12, 160), (2, 24, 24, 128), (1, 20, 24, 32), (2, 48, 48, 96)]
 VARIANTS = ["plain", "no_gf", "gz_in", "acc", "chan_scale"]
 EUNSUPPORTED = -3
-
-
-def _lib():
-    from causal_gen_amd import _lib
-
-    return _lib
-
-
-def _ceil(a, m):
-    return (a + m - 1) // m * m
-
-
-def _dgrad_image(w16, seg_off, seg_c):
-    """cgen_weight_prep mode 1 for a 1x1 conv, from the binary16-rounded OI weights: img[r][k] = W[k][seg_off + r]."""
-    co = w16.shape[0]
-    img = torch.zeros(_ceil(seg_c, 16), _ceil(_ceil(co, 8), 32) + 32, dtype=torch.float16)
-    img[:seg_c, :co] = w16[:, seg_off:seg_off + seg_c].t()
-    return img
 
 
 class Case:
@@ -336,27 +320,6 @@ def _small_hp(**over):
                          widths=[32, 64, 96, 128], z_max_res=24, z_dim=16, bs=3, **over)
 
 
-def _small_model(hp, dtype):
-    from causal_gen_amd import vae
-
-    torch.manual_seed(7)
-    m = vae.HVAE(hp)
-    g = torch.Generator().manual_seed(3)
-    with torch.no_grad():
-        for p in m.parameters():  # (the reference zero-initialises the prior heads: every conv gets weight)
-            p.add_(torch.randn(p.shape, generator=g) * 0.05)
-    m.compute_dtype = dtype
-    return m.cuda().train()
-
-
-def _batch(hp, B=3):
-    g = torch.Generator().manual_seed(1)
-    R = hp.input_res
-    x = (torch.randint(0, 256, (B, 1, R, R), generator=g).float() - 127.5) / 127.5
-    pa = torch.randn(B, hp.context_dim, generator=g)
-    return x.cuda(), pa.cuda()[..., None, None].expand(-1, -1, R, R)
-
-
 def _one_backward(monkeypatch, dtype, tail, exact="0", **over):
     monkeypatch.setenv("CGEN_LAT_TAIL", tail)
     monkeypatch.setenv("CGEN_LAT_TAIL_EXACT", exact)
@@ -366,10 +329,9 @@ def _one_backward(monkeypatch, dtype, tail, exact="0", **over):
     if drop is not None:
         m.decoder.is_drop_cond = True
         m.decoder.drop_cond = lambda: drop
-    x, pa = _batch(hp)
+    x, pa = _batch(hp, 3)
     eng = m.engine()
-    eng.rng_ptr()
-    eng.rng.copy_(torch.tensor([11, 0], dtype=torch.int64, device=eng.rng.device))
+    _seed(eng)
     l0 = eng.launches
     out = m(x, pa, beta=2.0)
     out["elbo"].backward()
@@ -423,7 +385,7 @@ def test_train_step_graph_replay_equals_eager_on_the_fused_path(monkeypatch):
     for use_graph in (False, True):
         hp = _small_hp(lr=2e-3, lr_warmup_steps=2)
         m = _small_model(hp, "f16")
-        x, pa = _batch(hp)
+        x, pa = _batch(hp, 3)
         torch.manual_seed(123)
         ts = TrainStep(m, SimpleNamespace(**vars(hp)), ema=True, use_graph=use_graph)
         for _ in range(3):

@@ -1,5 +1,5 @@
 """The latent tail of a DETERMINISTIC decoder layer (z = p_loc) as one launch each way: cgen_latent_tail_fwd / cgen_latent_tail_bwd
-called without q_loc / q_ls (csrc/latent_tail.hip), Engine.latent_tail_det_fwd / _bw_latent_tail_det, CGEN_LAT_TAIL_DET.
+called without q_loc / q_ls (csrc/latent_tail.hip), Engine.latent_tail_fwd without `q_loc` / _bw_latent_tail without `r`, CGEN_LAT_TAIL_DET.
 
 Everything is compared bit for bit against the separate launches the fused ones stand for:
   forward   cgen_conv2d (z_proj over [p_loc | pa], res1 = h, res2 = p_feat) and cgen_conv2d (z_feat_proj over [p_loc | p_feat]);
@@ -19,6 +19,8 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+from latent_tail_cases import _batch, _ceil, _dgrad_image, _fwd_image, _lib, _same, _seed, _small_model
+
 EUNSUPPORTED = -3
 SHAPES = [(2, 56, 56), (3, 46, 46)]
 # (C, Z): up to 64 channels the backward runs as one workgroup row, above as two; 160 takes the widest forward and backward instances
@@ -26,36 +28,6 @@ WIDTHS = [(32, 16), (64, 16), (32, 8), (64, 8), (96, 16), (160, 16)]
 CTX = {"ctx4const": (4, True), "ctx6mat": (6, False)}  # stride-0 parents zero padded to 8 | materialised parents
 GUARD, PATTERN = 512, 0x5B
 _ids = lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v)
-
-
-def _lib():
-    from causal_gen_amd import _lib
-
-    return _lib
-
-
-def _ceil(a, m):
-    return (a + m - 1) // m * m
-
-
-def _fwd_image(w16, seg_c):
-    """cgen_weight_prep mode 0 for a 1x1 conv: row = output channel, column = position in the concatenation of the input segments,
-    each padded to 8 channels; rows padded to 16, ceil32(columns) + 32 columns."""
-    co = w16.shape[0]
-    img = torch.zeros(_ceil(co, 16), _ceil(sum(_ceil(c, 8) for c in seg_c), 32) + 32, dtype=torch.float16)
-    src = dst = 0
-    for c in seg_c:
-        img[:co, dst:dst + c] = w16[:, src:src + c]
-        src, dst = src + c, dst + _ceil(c, 8)
-    return img
-
-
-def _dgrad_image(w16, seg_off, seg_c):
-    """cgen_weight_prep mode 1 for a 1x1 conv: img[r][k] = W[k][seg_off + r]."""
-    co = w16.shape[0]
-    img = torch.zeros(_ceil(seg_c, 16), _ceil(_ceil(co, 8), 32) + 32, dtype=torch.float16)
-    img[:seg_c, :co] = w16[:, seg_off:seg_off + seg_c].t()
-    return img
 
 
 class Arena:
@@ -320,27 +292,6 @@ def _small_hp(**over):
                          widths=[32, 32, 64, 64], z_max_res=32, z_dim=16, bs=2, **over)
 
 
-def _small_model(hp):
-    from causal_gen_amd import vae
-
-    torch.manual_seed(7)
-    m = vae.HVAE(hp)
-    g = torch.Generator().manual_seed(3)
-    with torch.no_grad():
-        for p in m.parameters():  # (the reference zero-initialises some heads: every conv gets weight)
-            p.add_(torch.randn(p.shape, generator=g) * 0.05)
-    m.compute_dtype = "f16"
-    return m.cuda().train()
-
-
-def _batch(hp, B=2):
-    g = torch.Generator().manual_seed(1)
-    R = hp.input_res
-    x = (torch.randint(0, 256, (B, 1, R, R), generator=g).float() - 127.5) / 127.5
-    pa = torch.randn(B, hp.context_dim, generator=g)
-    return x.cuda(), pa.cuda()[..., None, None].expand(-1, -1, R, R)
-
-
 def _one_pass(monkeypatch, knob, B=2, **env):
     monkeypatch.setenv("CGEN_LAT_TAIL_DET", knob)
     for k, v in env.items():
@@ -349,8 +300,7 @@ def _one_pass(monkeypatch, knob, B=2, **env):
     m = _small_model(hp)
     x, pa = _batch(hp, B)
     eng = m.engine()
-    eng.rng_ptr()
-    eng.rng.copy_(torch.tensor([11, 0], dtype=torch.int64, device=eng.rng.device))
+    _seed(eng)
     l0 = eng.launches
     out = m(x, pa, beta=2.0)
     out["elbo"].backward()
@@ -362,15 +312,6 @@ def _one_pass(monkeypatch, knob, B=2, **env):
     counts = SimpleNamespace(launches=eng.launches - l0, pairs=eng._conv.pairs, det=eng.lat_tails_det, det_fwd=eng.lat_tails_det_fwd,
                              sto=eng.lat_tails, sto_fwd=eng.lat_tails_fwd)
     return vals, grads, counts
-
-
-def _same(a, b):
-    (v1, g1), (v0, g0) = a, b
-    for k in v0:
-        assert torch.equal(v1[k], v0[k]), (k, v1[k], v0[k])
-    assert set(g1) == set(g0)
-    for n in g0:
-        assert torch.equal(g1[n], g0[n]), (n, float((g1[n].double() - g0[n].double()).abs().max()))
 
 
 @pytest.mark.gpu
@@ -416,7 +357,7 @@ def test_train_step_graph_replay_equals_eager_and_the_separate_launches(monkeypa
         monkeypatch.setenv("CGEN_LAT_TAIL_DET", knob)
         hp = _small_hp(lr=2e-3, lr_warmup_steps=2)
         m = _small_model(hp)
-        x, pa = _batch(hp)
+        x, pa = _batch(hp, 2)
         torch.manual_seed(123)
         ts = TrainStep(m, SimpleNamespace(**vars(hp)), ema=True, use_graph=use_graph)
         for _ in range(3):

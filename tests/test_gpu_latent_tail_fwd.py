@@ -22,6 +22,8 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+from latent_tail_cases import _batch, _ceil, _fwd_image, _lib, _same, _seed, _small_model
+
 EUNSUPPORTED = -3
 # (n, h, w, C, Z): conv_smallp serves the first five (<= 6 000 pixels; 20 * 24 * 16 elements leave a partial last KL chunk, 24 * 24
 # has 4.5 chunks per sample), conv_px the last two (6 912 and 6 336 pixels; the second with the 7-K-step instance and partial chunks)
@@ -34,29 +36,6 @@ VARIANTS = {
     "eps-paconst-ctx20-cf_same": dict(eps=True, pa_const=True, ctx=20, zf="same"),
 }
 LAT_CHUNK = 2048
-
-
-def _lib():
-    from causal_gen_amd import _lib
-
-    return _lib
-
-
-def _ceil(a, m):
-    return (a + m - 1) // m * m
-
-
-def _fwd_image(w16, seg_c):
-    """cgen_weight_prep mode 0 for a 1x1 conv, from the binary16-rounded OI weights: row = output channel, column = position in the
-    concatenation of the input segments, each padded to 8 channels; rows padded to 16, ceil32(columns) + 32 columns."""
-    co = w16.shape[0]
-    k8 = sum(_ceil(c, 8) for c in seg_c)
-    img = torch.zeros(_ceil(co, 16), _ceil(k8, 32) + 32, dtype=torch.float16)
-    src = dst = 0
-    for c in seg_c:
-        img[:co, dst:dst + c] = w16[:, src:src + c]
-        src, dst = src + c, dst + _ceil(c, 8)
-    return img
 
 
 class Case:
@@ -333,37 +312,11 @@ def _small_hp(**over):
                          widths=[32, 64, 96, 128], z_max_res=24, z_dim=16, bs=3, **over)
 
 
-def _small_model(hp):
-    from causal_gen_amd import vae
-
-    torch.manual_seed(7)
-    m = vae.HVAE(hp)
-    g = torch.Generator().manual_seed(3)
-    with torch.no_grad():
-        for p in m.parameters():  # (the reference zero-initialises the prior heads: every conv gets weight)
-            p.add_(torch.randn(p.shape, generator=g) * 0.05)
-    m.compute_dtype = "f16"
-    return m.cuda().train()
-
-
-def _batch(hp, B=3):
-    g = torch.Generator().manual_seed(1)
-    R = hp.input_res
-    x = (torch.randint(0, 256, (B, 1, R, R), generator=g).float() - 127.5) / 127.5
-    pa = torch.randn(B, hp.context_dim, generator=g)
-    return x.cuda(), pa.cuda()[..., None, None].expand(-1, -1, R, R)
-
-
-def _seed(eng):
-    eng.rng_ptr()
-    eng.rng.copy_(torch.tensor([11, 0], dtype=torch.int64, device=eng.rng.device))
-
-
 def _one_pass(monkeypatch, knob, **over):
     monkeypatch.setenv("CGEN_LAT_TAIL_FWD", knob)
     hp = _small_hp(**over)
     m = _small_model(hp)
-    x, pa = _batch(hp)
+    x, pa = _batch(hp, 3)
     eng = m.engine()
     _seed(eng)
     l0 = eng.launches
@@ -392,14 +345,10 @@ def test_model_one_launch_against_three(monkeypatch, mode):
     assert t0 == 0 and t1 == 7, (t0, t1)
     print("forward launches: three-launch path %d, fused %d" % (n0, n1))
     assert n0 - n1 == 2 * 6 + 1, (n0, n1)
-    for k in v0:
-        assert torch.equal(v1[k], v0[k]), (k, v1[k], v0[k])
     assert len(z1) == len(z0) == 7
     for a, b in zip(z1, z0):
         assert torch.equal(a, b)
-    assert set(g1) == set(g0)
-    for n in g0:
-        assert torch.equal(g1[n], g0[n]), (n, float((g1[n].double() - g0[n].double()).abs().max()))
+    _same((v1, g1), (v0, g0))
 
 
 @pytest.mark.gpu
@@ -412,7 +361,7 @@ def test_train_step_graph_replay_equals_eager_on_the_fused_path(monkeypatch):
     for use_graph in (False, True):
         hp = _small_hp(lr=2e-3, lr_warmup_steps=2)
         m = _small_model(hp)
-        x, pa = _batch(hp)
+        x, pa = _batch(hp, 3)
         torch.manual_seed(123)
         ts = TrainStep(m, SimpleNamespace(**vars(hp)), ema=True, use_graph=use_graph)
         for _ in range(3):
