@@ -6,7 +6,8 @@ __version__ = "0.1.0"
 
 
 _LAZY = {"DeviceDataset": "data", "DeviceLoader": "data", "PgmCounterfactual": "pgm_cf", "DevicePGM": "pgm_cf",
-         "ChestPredictor": "predictor_resnet", "ChestPredictorTrainStep": "predictor_resnet_train"}
+         "ChestPredictor": "predictor_resnet", "ChestPredictorTrainStep": "predictor_resnet_train",
+         "CfTrainStep": "cf_train"}
 
 
 def __getattr__(name):  # the data pipeline's and the device PGM's classes, re-exported without importing torch at package import

@@ -80,6 +80,21 @@ class AdamwArgs(C.Structure):
                 ("state_dev", C.c_void_p)]
 
 
+class CfLagrangeArgs(C.Structure):
+    """cgen_cf_lagrange_args: the Lagrangian of counterfactual fine-tuning -- inputs, constants and the five output blocks."""
+    _fields_ = [("out3", C.c_void_p), ("aux_sum", C.c_void_p), ("aux_add", C.c_void_p), ("lmbda", C.c_void_p), ("beta_dev", C.c_void_p),
+                ("nonfinite", C.c_void_p), ("n_nonfinite", C.c_int32), ("inv_b", C.c_float), ("eps", C.c_float), ("damping", C.c_float),
+                ("seed_scale", C.c_float), ("beta", C.c_float), ("res", C.c_void_p), ("coef", C.c_void_p), ("gsq_slot", C.c_void_p),
+                ("gate", C.c_void_p), ("sums", C.c_void_p)]
+
+
+class LagrangeStepArgs(C.Structure):
+    """cgen_lagrange_step_args: the multiplier, its moments and EMA, its gradient and the tail's state vector."""
+    _fields_ = [("lmbda", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p), ("g", C.c_void_p), ("state_dev", C.c_void_p),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("ema_beta", C.c_float),
+                ("ema_update_after", C.c_int32)]
+
+
 class PredHead(C.Structure):
     _fields_ = [("c", C.c_int32), ("res", C.c_int32), ("width", C.c_int32), ("nout", C.c_int32), ("ctx", C.c_int32),
                 ("kind", C.c_int32), ("tanh_loc", C.c_int32), ("obs_stride", C.c_int32), ("std_fixed", C.c_float),
@@ -289,6 +304,10 @@ PROTOTYPES = {
     "cgen_clip_decide": [vp, i32, vp, f32, f32, vp, vp],
     "cgen_adamw_ema": [C.POINTER(AdamwArgs), vp],
     "cgen_step_commit": [vp, vp],
+    "cgen_adamw_ema_const_lr": [C.POINTER(AdamwArgs), vp],
+    "cgen_nonfinite_partial": [i32, i32, i32, i32, View, vp, i32, vp],
+    "cgen_cf_lagrange": [C.POINTER(CfLagrangeArgs), vp],
+    "cgen_lagrange_step": [C.POINTER(LagrangeStepArgs), vp],
     "cgen_predictor_supported": [C.POINTER(PredHead), i32],
     "cgen_predictor_workspace": [C.POINTER(PredHead), i32, C.POINTER(i64)],
     "cgen_predictor_fwd": [C.POINTER(PredHead), i32, i32, vp, vp, vp, vp, vp, vp],

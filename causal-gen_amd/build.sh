@@ -8,7 +8,7 @@ set -e
 cd "$(dirname "$0")"
 OUT=libcgen_hip.so
 NOPK="-Xclang -target-feature -Xclang -packed-fp32-ops"
-SRCS="csrc/runtime.hip csrc/block.hip csrc/block4.hip csrc/conv.hip csrc/wgrad.hip csrc/multitensor.hip csrc/wgrad3.hip csrc/elementwise.hip csrc/augment.hip csrc/latent.hip csrc/latent_tail.hip csrc/likelihood.hip csrc/optim.hip csrc/predictor.hip csrc/cf_eval.hip csrc/pgm.hip csrc/pgm_cf.hip"
+SRCS="csrc/runtime.hip csrc/block.hip csrc/block4.hip csrc/conv.hip csrc/wgrad.hip csrc/multitensor.hip csrc/wgrad3.hip csrc/elementwise.hip csrc/augment.hip csrc/latent.hip csrc/latent_tail.hip csrc/likelihood.hip csrc/optim.hip csrc/cf_train.hip csrc/predictor.hip csrc/cf_eval.hip csrc/pgm.hip csrc/pgm_cf.hip"
 mkdir -p build
 OBJS=""
 pids=""

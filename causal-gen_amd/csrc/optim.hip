@@ -3,6 +3,7 @@
 //   AdamW + EMA.  All schedule arithmetic (LambdaLR warm-up, Adam bias correction, EMA warm-up decay) is derived on
 //   the device from the count of successful optimiser steps, so the host never has to read the skip decision.
 #include "common.h"
+#include "optim_sched.h"
 
 namespace cgen {
 
@@ -45,23 +46,20 @@ struct AdamP {
   const float* state;
 };
 
+// CONST_LR: no LambdaLR (train_cf.py has no scheduler): lr as given on every step
+template <bool CONST_LR>
 __global__ __launch_bounds__(256) void adamw_ema_kernel(AdamP a) {
   if (a.state[3] != 0.f) return;  // skipped update: parameters, moments and EMA all untouched
   const float clip = a.state[2];
   const int t0 = (int)a.state[5];  // successful steps before this one
   const float t = (float)(t0 + 1);
-  const float lr = a.lr * (t0 > a.warmup_steps ? 1.f : (float)t0 / (float)a.warmup_steps);  // LambdaLR(linear_warmup)
+  const float lr = CONST_LR ? a.lr : a.lr * (t0 > a.warmup_steps ? 1.f : (float)t0 / (float)a.warmup_steps);  // LambdaLR(linear_warmup)
   const float bc1 = 1.f - powf(a.beta1, t);
   const float bc2s = sqrtf(1.f - powf(a.beta2, t));
   const float step = lr / bc1;
   const float decay_w = 1.f - lr * a.wd;
   // EMA (utils.py:169-193): calls that see step <= update_after (+1: first 'initted' call) are straight copies
-  float ema_decay = -1.f;
-  if (t0 > a.ema_update_after + 1) {
-    const float epoch = (float)(t0 - a.ema_update_after);
-    const float d = 1.f - 1.f / (1.f + epoch);
-    ema_decay = d < a.ema_beta ? d : a.ema_beta;
-  }
+  const float ema_decay = ema_decay_of(t0, a.ema_update_after, a.ema_beta);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.count; i += (int64_t)gridDim.x * 256) {
     const float g = a.g[i] * clip;
     float p = a.p[i] * decay_w;
@@ -99,10 +97,7 @@ extern "C" int cgen_clip_decide(const float* partial, int32_t nblk, const float*
   return check_launch("cgen_clip_decide");
 }
 
-extern "C" int cgen_adamw_ema(const cgen_adamw_args* a, cgen_stream_t stream) {
-  CGEN_REQUIRE(a && a->p && a->g && a->m && a->v && a->state_dev && a->count >= 0, "cgen_adamw_ema: bad args");
-  // (LambdaLR(linear_warmup) divides by the warm-up length: 0 would make the first step's lr 0/0 and every weight NaN)
-  CGEN_REQUIRE(a->warmup_steps > 0, "cgen_adamw_ema: warmup_steps must be > 0 (got %d)", a->warmup_steps);
+static int adamw_launch(const cgen_adamw_args* a, bool const_lr, cgen_stream_t stream, const char* what) {
   if (a->count == 0) return CGEN_OK;
   AdamP p;
   p.p = a->p; p.g = a->g; p.m = a->m; p.v = a->v; p.ema = a->ema; p.count = a->count;
@@ -110,8 +105,21 @@ extern "C" int cgen_adamw_ema(const cgen_adamw_args* a, cgen_stream_t stream) {
   p.warmup_steps = a->warmup_steps; p.ema_update_after = a->ema_update_after; p.state = a->state_dev;
   int64_t b = (a->count + 255) / 256;
   if (b > 4096) b = 4096;
-  hipLaunchKernelGGL(adamw_ema_kernel, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p);
-  return check_launch("cgen_adamw_ema");
+  if (const_lr) hipLaunchKernelGGL(adamw_ema_kernel<true>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(adamw_ema_kernel<false>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p);
+  return check_launch(what);
+}
+
+extern "C" int cgen_adamw_ema(const cgen_adamw_args* a, cgen_stream_t stream) {
+  CGEN_REQUIRE(a && a->p && a->g && a->m && a->v && a->state_dev && a->count >= 0, "cgen_adamw_ema: bad args");
+  // (LambdaLR(linear_warmup) divides by the warm-up length: 0 would make the first step's lr 0/0 and every weight NaN)
+  CGEN_REQUIRE(a->warmup_steps > 0, "cgen_adamw_ema: warmup_steps must be > 0 (got %d)", a->warmup_steps);
+  return adamw_launch(a, false, stream, "cgen_adamw_ema");
+}
+
+extern "C" int cgen_adamw_ema_const_lr(const cgen_adamw_args* a, cgen_stream_t stream) {
+  CGEN_REQUIRE(a && a->p && a->g && a->m && a->v && a->state_dev && a->count >= 0, "cgen_adamw_ema_const_lr: bad args");
+  return adamw_launch(a, true, stream, "cgen_adamw_ema_const_lr");
 }
 
 extern "C" int cgen_step_commit(float* state_dev, cgen_stream_t stream) {

@@ -49,6 +49,39 @@ class Flat:
         self.flat_p, self.p_off = flatten(self.params, dev)
 
 
+def ranges_where(eng, pred):
+    """Contiguous [lo, hi) ranges of an engine's flat buffers covered by the parameters `pred` holds for (neighbours are joined)."""
+    rs, cur = [], None
+    for p in eng.params:
+        o, k = eng.p_off[id(p)], p.numel()
+        if not pred(p):
+            cur = None
+        elif cur is not None and cur[1] == o:
+            cur[1] = o + k
+        else:
+            cur = [o, o + k]
+            rs.append(cur)
+    return [(a, b) for a, b in rs]
+
+
+def mark_weights_written(*models):
+    """The fused AdamW / EMA kernel writes the flat parameter buffers through raw pointers, which torch's version counters do not
+    see: tell the engines of `models` (None entries allowed) that their weight images are stale, so the next inference call
+    re-images before it runs."""
+    for mod in models:
+        eng = None if mod is None else mod.__dict__.get("_eng")
+        if eng is not None:
+            eng.weights_dirty = True
+
+
+def pin_drop_cond(model):
+    """``drop_cond`` of a conditional-prior decoder is a host draw: draw it, pin the outcome for this step's launches and return
+    it (a captured step is keyed by it)."""
+    drop = type(model.decoder).drop_cond(model.decoder)
+    model.decoder.__dict__["drop_cond"] = lambda d=drop: d
+    return drop
+
+
 def capture(fn):
     """`fn()` captured into a hipGraph, after an eager run of the same launches by the caller.  Returns (graph, fn's result)."""
     torch.cuda.synchronize()
@@ -60,20 +93,25 @@ def capture(fn):
 
 # AdamW(lr, betas, eps, wd) under LambdaLR(linear_warmup(lr_warmup_steps)), clip_grad_norm_(grad_clip) and an EMA(ema_rate) with
 # update_after_step = ema_update_after; a norm at or above grad_skip drops the step (inf: only a non-finite one or a NaN loss does)
-HyperParams = namedtuple("HyperParams", "lr betas eps wd grad_clip grad_skip lr_warmup_steps ema_rate ema_update_after")
+# `const_lr` (defaulted: the nine-field constructions mean what they always did): no LambdaLR, `lr` on every step, `lr_warmup_steps`
+# unused -- train_cf.py has no scheduler, and linear_warmup(n) would give the first step lr = 0 for every n >= 1
+HyperParams = namedtuple("HyperParams", "lr betas eps wd grad_clip grad_skip lr_warmup_steps ema_rate ema_update_after const_lr",
+                         defaults=(False,))
 
 
 class StepTail:
     """Global grad-norm -> clip / skip predicate -> fused AdamW + EMA -> step counter commit, on flat f32 buffers of `n` elements.
     Owns the moments ``m`` / ``v``, the step ``state`` and the norm's ``partial`` sums (`norm_blocks` of them: their number fixes
-    the order of the norm's sum, hence its bits)."""
+    the order of the norm's sum, hence its bits).  `extra_norm_slots`: further sums of squares that belong to the norm and lie outside
+    the flat gradient (``extra_slot(i)`` is where their owner writes them before ``run``; ``cgen_sumsq_partial`` fills the first
+    `norm_blocks` entries, ``cgen_clip_decide`` sums all)."""
 
-    def __init__(self, lib, n, device, norm_blocks):
-        self.lib, self.n, self.norm_blocks = lib, n, norm_blocks
+    def __init__(self, lib, n, device, norm_blocks, extra_norm_slots=0):
+        self.lib, self.n, self.norm_blocks, self.extra_norm_slots = lib, n, norm_blocks, int(extra_norm_slots)
         self.m = torch.zeros(n, device=device)
         self.v = torch.zeros(n, device=device)
         self.state = torch.zeros(STATE_FLOATS, device=device)
-        self.partial = torch.zeros(norm_blocks, device=device)
+        self.partial = torch.zeros(norm_blocks + self.extra_norm_slots, device=device)
         self._zero = None  # zero gradient / moments of the `ema_only` passes
 
     def _adamw(self, hp, p, g, m, v, ema, count, lr, wd, stream):
@@ -82,16 +120,24 @@ class StepTail:
         q.lr, q.beta1, q.beta2, q.eps, q.wd = lr, hp.betas[0], hp.betas[1], hp.eps, wd
         q.ema_beta, q.warmup_steps, q.ema_update_after = hp.ema_rate, hp.lr_warmup_steps, hp.ema_update_after
         q.state_dev = self.state.data_ptr()
-        self.lib.adamw_ema(C.byref(q), stream)
+        (self.lib.adamw_ema_const_lr if hp.const_lr else self.lib.adamw_ema)(C.byref(q), stream)
 
-    def run(self, hp, p, g, ema, out3, stream, ranges=None, ema_only=()):
+    def extra_slot(self, i):
+        """Device address of the i-th extra sum-of-squares slot of the norm."""
+        if not 0 <= i < self.extra_norm_slots:
+            raise IndexError(f"StepTail: extra norm slot {i} of {self.extra_norm_slots}")
+        return self.partial.data_ptr() + 4 * (self.norm_blocks + i)
+
+    def run(self, hp, p, g, ema, out3, stream, ranges=None, ema_only=(), before_commit=None):
         """One optimiser step of the flat parameters `p` on the flat gradient `g` (`ema`: the averaged copy, or None).  `out3`
         (or None): device [elbo, nll, kl], a NaN in nll or kl drops the step.  `ranges`: the [lo, hi) element ranges to update,
         one launch each (default: everything); the norm is always of the whole of `g`.  `ema_only`: (p_ptr, ema_ptr, count)
-        regions that are averaged with the step's decay and otherwise left alone (lr = wd = 0 on a zero gradient)."""
+        regions that are averaged with the step's decay and otherwise left alone (lr = wd = 0 on a zero gradient).
+        `before_commit(stream)`: launches of the caller's between the last ``adamw_ema`` and ``step_commit`` -- they see this step's
+        clip coefficient and skip flag and the count of successful steps BEFORE it, as ``adamw_ema`` does."""
         lib, state = self.lib, self.state.data_ptr()
         lib.sumsq_partial(g.data_ptr(), g.numel(), self.partial.data_ptr(), self.norm_blocks, stream)
-        lib.clip_decide(self.partial.data_ptr(), self.norm_blocks, None if out3 is None else out3.data_ptr(), hp.grad_clip,
+        lib.clip_decide(self.partial.data_ptr(), self.norm_blocks + self.extra_norm_slots, None if out3 is None else out3.data_ptr(), hp.grad_clip,
                         hp.grad_skip, state, stream)
         for lo, hi in [(0, g.numel())] if ranges is None else ranges:
             self._adamw(hp, p.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo, self.m.data_ptr() + 4 * lo, self.v.data_ptr() + 4 * lo,
@@ -103,11 +149,17 @@ class StepTail:
             if z.shape[1] < count:
                 raise ValueError(f"StepTail: an ema_only region of {count} elements after one of {z.shape[1]}")
             self._adamw(hp, p_ptr, z[0].data_ptr(), z[1].data_ptr(), z[2].data_ptr(), ema_ptr, count, 0.0, 0.0, stream)
+        if before_commit is not None:
+            before_commit(stream)
         lib.step_commit(state, stream)
 
     def stats(self):
         """Host read of the device-side step state (one sync; call every N steps, not every step)."""
-        s = self.state.cpu().tolist()
+        return self.stats_of(self.state.cpu().tolist())
+
+    @staticmethod
+    def stats_of(s):
+        """``stats()`` from the state vector's floats already on the host (a caller that reads more in the same copy)."""
         return dict(grad_norm=s[NORM], clip_coef=s[CLIP_COEF], skipped_last=bool(s[SKIP]), n_skipped=int(s[N_SKIPPED]),
                     opt_steps=int(s[OPT_STEPS]))
 

@@ -21,7 +21,8 @@ import torch
 
 from . import _lib, dp
 from .engine import StaticParents, compact_parents
-from .step_tail import CAPTURE_MODE, N_NONFINITE, N_SKIPPED, OPT_STEPS, STATE_FLOATS, HyperParams, StepTail, capture, check_warmup
+from .step_tail import (CAPTURE_MODE, N_NONFINITE, N_SKIPPED, OPT_STEPS, STATE_FLOATS, HyperParams, StepTail, capture, check_warmup,
+                        mark_weights_written, pin_drop_cond, ranges_where)
 
 
 def preprocess_batch(args, batch, expand_pa=False):
@@ -230,18 +231,7 @@ class TrainStep:
 
     def _ranges_where(self, pred):
         """Contiguous [lo, hi) ranges of the flat buffers covered by the parameters `pred` holds for (neighbours are joined)."""
-        eng = self.eng
-        rs, cur = [], None
-        for p in eng.params:
-            o, k = eng.p_off[id(p)], p.numel()
-            if not pred(p):
-                cur = None
-            elif cur is not None and cur[1] == o:
-                cur[1] = o + k
-            else:
-                cur = [o, o + k]
-                rs.append(cur)
-        return [(a, b) for a, b in rs]
+        return ranges_where(self.eng, pred)
 
     # -- gradient all-reduce overlapped with the backward pass (north_star; SURVEY 5 / 8e) -------------------------
     def _allreduce_ranges(self, ranges, works):
@@ -334,10 +324,7 @@ class TrainStep:
         """The fused AdamW / EMA kernel writes both flat parameter buffers through raw pointers, which torch's version
         counters do not see: tell the engines (model and EMA copy) that their weight images are stale, so the next
         inference call (validation on ``ema_model``, sampling, counterfactuals) re-images before it runs."""
-        for mod in (self.model, self.ema_model):
-            eng = None if mod is None else mod.__dict__.get("_eng")
-            if eng is not None:
-                eng.weights_dirty = True
+        mark_weights_written(self.model, self.ema_model)
 
     # -- public -------------------------------------------------------------------------------------------
     def step(self, x, pa):
@@ -385,8 +372,7 @@ class TrainStep:
         m = self.model
         drop = (1, 1)
         if m.cond_prior:  # host draw (shared across DP ranks through the common seed), one graph per outcome
-            drop = type(m.decoder).drop_cond(m.decoder)
-            m.decoder.__dict__["drop_cond"] = lambda d=drop: d
+            drop = pin_drop_cond(m)
         # (beta is device data: the warm-up schedule replays the same graph; virtual and materialised parents are different graphs)
         static = hasattr(x, "emit")  # a device-side input (step_from): its buffers are static already, its identity keys the graph
         return (tuple(x.shape), x.dtype, drop, do_step, tuple(pa.shape), compact_parents(pa) is not None, x.key if static else None)

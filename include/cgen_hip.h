@@ -1095,6 +1095,40 @@ typedef struct cgen_adamw_args {
 int cgen_adamw_ema(const cgen_adamw_args* a, cgen_stream_t);
 /* opt_steps += 1 unless the step was skipped (run once after all cgen_adamw_ema launches of a step) */
 int cgen_step_commit(float* state_dev, cgen_stream_t);
+/* cgen_adamw_ema without the LambdaLR warm-up: lr as given on every step (train_cf.py has no scheduler); warmup_steps is ignored. */
+int cgen_adamw_ema_const_lr(const cgen_adamw_args* a, cgen_stream_t);
+
+/* ---- counterfactual fine-tuning (train_cf.py:140-180, dscm.py:75-88): what CfTrainStep adds to the tail above (csrc/cf_train.hip).
+ * Fixed-order sums, no atomics, bit-identical reruns; every call only enqueues.
+ *
+ * cgen_nonfinite_partial: partial[b] = number of NaN / +-inf among block b's share of the n*h*w*v.c logical elements of the NHWC
+ * view `v` (CGEN_F32 or CGEN_F16; v.sw >= v.c, a padded channel stride is skipped over).  Logical element i = ((n h + y) w + x) c + ch
+ * belongs to block (i / 256) % nblk, the assignment of cgen_sumsq_partial.  Fewer than 2^31 elements. */
+int cgen_nonfinite_partial(int32_t dtype, int32_t n, int32_t h, int32_t w, cgen_view v, int32_t* partial /*[nblk]*/, int32_t nblk,
+                           cgen_stream_t);
+/* cgen_cf_lagrange (one workgroup).  With c = eps - elbo, w = lmbda - damping c (the damping term under stop-gradient):
+ *   res  = {loss = aux_loss - w c, aux_loss = (aux_sum [+ aux_add]) inv_b, g_lmbda = -c, w}
+ *   coef = {w seed_scale, w beta seed_scale, beta}: the engine's likelihood / KL gradient seeds, seed_scale = S / (B dims)
+ *   *gsq_slot = g_lmbda^2: the multiplier's slot among the gradient norm's partial sums
+ *   gate = {loss, bad ? NaN : nll, kl} for cgen_clip_decide's out3; bad = loss non-finite or any of the n_nonfinite counts > 0
+ *   sums = {loss, aux_loss, elbo, nll, kl, n, n_bad, -}: += the step's values and n += 1 unless bad, else n_bad += 1
+ * beta is read from beta_dev when that is not NULL. */
+typedef struct cgen_cf_lagrange_args {
+  const float* out3; const float* aux_sum; const float* aux_add /* may be NULL */; const float* lmbda;
+  const float* beta_dev /* may be NULL */; const int32_t* nonfinite; int32_t n_nonfinite;
+  float inv_b, eps, damping, seed_scale, beta;
+  float* res /*[4]*/; float* coef /*[3]*/; float* gsq_slot; float* gate /*[3]*/; float* sums /*[8]*/;
+} cgen_cf_lagrange_args;
+int cgen_cf_lagrange(const cgen_cf_lagrange_args* a, cgen_stream_t);
+/* cgen_lagrange_step (one thread; train_cf.py:174-177), after the parameters' cgen_adamw_ema launches and before cgen_step_commit:
+ * nothing on a skipped step; else AdamW(maximize=True, wd = 0, constant lr) on the gradient -g[0] clip_coef with cgen_adamw_ema's
+ * moment updates and bias corrections, then lmbda = max(lmbda, 0), then the EMA of the clamped value with cgen_adamw_ema's decay. */
+typedef struct cgen_lagrange_step_args {
+  float* lmbda; float* m; float* v; float* ema /* may be NULL */; const float* g; const float* state_dev;
+  float lr, beta1, beta2, eps, ema_beta;
+  int32_t ema_update_after;
+} cgen_lagrange_step_args;
+int cgen_lagrange_step(const cgen_lagrange_step_args* a, cgen_stream_t);
 
 /* Philox normal fill (f32 contiguous) -- exposed for tests of the in-kernel generator */
 int cgen_philox_normal(float* out, int64_t count, const uint64_t* rng, uint32_t stream_id, cgen_stream_t);
