@@ -32,7 +32,8 @@ import torch
 
 from . import _lib
 from .engine import StaticParents, compact_parents
-from .step_tail import STATE_FLOATS, HyperParams, StepTail, capture, mark_weights_written, pin_drop_cond, ranges_where
+from .step_tail import (STATE_FLOATS, HyperParams, StepTail, capture, check_index, mark_weights_written, normalize_columns, pin_drop_cond,
+                        ranges_where)
 
 LMBDA, LM, LV, LEMA = range(4)
 S_LOSS, S_AUX, S_ELBO, S_NLL, S_KL, S_N, S_BAD = range(7)
@@ -69,7 +70,7 @@ class CfTrainStep:
         self.lib = _lib.require_gpu()
         self.dscm, self.args, self.use_graph = dscm, args, use_graph
         self.lr, self.lr_lagrange = float(lr), float(lr_lagrange)
-        self.columns = None if columns is None else {k: (int(v), 1) if isinstance(v, int) else (int(v[0]), int(v[1])) for k, v in columns.items()}
+        self.columns = normalize_columns(columns)
         dev = torch.device(device)
         self.vae, self.pred = dscm.vae.to(dev), dscm.predictor.to(dev)
         self.eng = eng = self.vae.engine()
@@ -114,23 +115,19 @@ class CfTrainStep:
     def _pred_records(self, B, xshape, at, dense):
         """The predictor's head records for a static batch: ``at(var)`` = (address, row stride in floats) of a scored variable's
         rows, ``dense[var]`` the contiguous [B, k] buffer of a context variable (predictor._records on caller-owned buffers)."""
+        from .predictor import fill_head
+
         heads = self.pred._heads()
         recs = (_lib.PredHead * len(heads))()
         keep = []
         for r, hd in zip(recs, heads):
-            cnn = hd.cnn
-            if tuple(cnn.in_shape) != tuple(xshape[1:]):
-                raise ValueError(f"predictor head for {hd.var}: built for input {cnn.in_shape}, got {tuple(xshape[1:])}")
-            wb = cnn.folded(self.device)
+            y = dense[hd.ctx_var] if hd.cnn.context_dim else None
+            fill_head(r, hd, xshape, self.pred.std_fixed, None if y is None else y.shape[1])
+            wb = hd.cnn.folded(self.device)
             keep.append(wb)
-            r.c, r.res, r.width, r.nout, r.ctx = xshape[1], xshape[-1], cnn.width, cnn.num_outputs, cnn.context_dim
-            r.kind, r.tanh_loc, r.std_fixed = hd.kind, int(hd.tanh_loc), float(self.pred.std_fixed)
             for i, (w, b) in enumerate(wb):
                 r.w[i], r.b[i] = w.data_ptr(), b.data_ptr()
-            if cnn.context_dim:
-                y = dense[hd.ctx_var]
-                if y.shape[1] != cnn.context_dim:
-                    raise ValueError(f"predictor head for {hd.var}: context {hd.ctx_var} has {y.shape[1]} columns, expected {cnn.context_dim}")
+            if y is not None:
                 r.y = y.data_ptr()
             r.obs, r.obs_stride = at(hd.var)
         return recs, keep
@@ -211,8 +208,7 @@ class CfTrainStep:
     def _static_from(self, ds, index, train):
         from .data import AugmentedInput
 
-        if index.dtype != torch.int64 or index.dim() != 1 or index.device.type != "cuda":
-            raise ValueError("CfTrainStep.step_from: the index must be a device int64 vector")
+        check_index(index, "CfTrainStep.step_from")
         B = int(index.numel())
         key = ("from", ds.key(train), B) + self._drop_key()
         ent = self._ents.get(key)

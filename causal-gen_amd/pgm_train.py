@@ -6,7 +6,8 @@
 
 ``loss`` is ``pgm.nll``: minus the summed log-probability of every parent, divided by the batch size.  The optimiser is the
 reference's ``AdamW(lr, betas, eps, wd)`` under ``LambdaLR(linear_warmup(lr_warmup_steps))`` with ``clip_grad_norm_`` and
-``EMA(beta=ema_rate)``; the step tail is ``TrainStep``'s and ``PredictorTrainStep``'s (csrc/optim.hip).  There is no host
+``EMA(beta=ema_rate)``; the step tail (csrc/optim.hip) and everything around it that is not the PGM's own -- constructor, ``_run``,
+checkpoint pair -- is ``step_tail.SupStep``'s, shared with ``PredictorTrainStep`` and ``ChestPredictorTrainStep``.  There is no host
 synchronisation inside a step, nothing is read back, and the step is captured into one hipGraph per batch shape after an eager
 first step.  The mechanisms come from ``pgm.mechanisms()``, the list ``pgm.log_prob`` is driven by, so the host density is the
 oracle of this path.  The base ``*_base_loc`` / ``*_base_scale`` buffers are not trained.
@@ -14,7 +15,6 @@ oracle of this path.  The base ``*_base_loc`` / ``*_base_scale`` buffers are not
 A PGM the kernel does not serve (a hidden width above 64, more than three hidden layers, more than eight bins, another
 activation) raises ``ValueError``; nothing falls back to host torch.
 """
-import copy
 import ctypes as C
 
 import torch
@@ -22,7 +22,7 @@ from torch import nn
 
 from . import _lib
 from .pgm import ConditionalAffine, DenseNN, LinearSpline
-from .step_tail import NORM, Flat, HyperParams, StepTail, capture, check_warmup
+from .step_tail import Flat, SupStep, check_index
 
 _KINDS = {"bernoulli": _lib.PGM_BERNOULLI, "categorical": _lib.PGM_CATEGORICAL, "spline": _lib.PGM_SPLINE, "affine": _lib.PGM_AFFINE,
           "gumbel_max": _lib.PGM_GUMBEL_MAX}
@@ -116,46 +116,27 @@ def build_records(pgm, columns, ncol, grad_ptr=None):
     return recs
 
 
-class PgmTrainStep:
+class PgmTrainStep(SupStep):
     NORM_BLOCKS = 64
 
     def __init__(self, pgm, lr=1e-4, wd=0.1, betas=(0.9, 0.999), eps=1e-8, grad_clip=200.0, lr_warmup_steps=1, ema_rate=0.999, ema=True,
                  use_graph=True, ema_update_after=100, columns=None, ncol=None, device="cuda"):
-        check_warmup(lr_warmup_steps)
-        self.lib = _lib.require_gpu()
-        dev = self.device = torch.device(device)
-        # (no norm threshold in sup_epoch: only a non-finite norm or a NaN loss drops the step)
-        self.hp = HyperParams(float(lr), (float(betas[0]), float(betas[1])), float(eps), float(wd), float(grad_clip), float("inf"),
-                              int(lr_warmup_steps), float(ema_rate), int(ema_update_after))
-        self.use_graph = use_graph
         if columns is None:
             columns, width = default_columns(pgm)
             ncol = width if ncol is None else ncol
-        self.columns = dict(columns)
+        self.columns = dict(columns)  # {variable: FIRST column} (a one-hot variable's width is its mechanism's)
         if ncol is None:
             raise ValueError("PgmTrainStep: `ncol` (the table's width) is needed with named columns")
         self.ncol = int(ncol)
-        self.ema_model = None
-        if ema:
-            self.ema_model = copy.deepcopy(pgm)
-            self.ema_model.requires_grad_(False)
-            self._ema = Flat(self.ema_model.to(dev).named_parameters(), dev)
-        self.model = pgm
-        self._on = Flat(pgm.to(dev).named_parameters(), dev)
-        n = self._on.flat_p.numel()
-        self.flat_g = torch.zeros(n, device=dev)
-        self.tail = StepTail(self.lib, n, dev, self.NORM_BLOCKS)
-        self.stats = self.tail.stats  # host read of the device-side step state (one sync)
-        self.m, self.v, self.state, self.partial = self.tail.m, self.tail.v, self.tail.state, self.tail.partial
+        super().__init__(pgm, lr, wd, betas, eps, grad_clip, lr_warmup_steps, ema_rate, ema, use_graph, ema_update_after, device)
         on = self._on
         self.recs = build_records(pgm, self.columns, self.ncol, {id(p): self.flat_g.data_ptr() + 4 * o for p, o in zip(on.params, on.p_off)})
         self.nmech = len(self.recs)
-        self.out3 = torch.zeros(3, device=dev)  # [-, summed log-probability, 0]: what cgen_clip_decide tests for NaN
-        self.res = torch.zeros(2, device=dev)   # [mean loss, gradient norm] of the last step
-        self._statics, self._graphs = {}, {}
-        self.it = 0
 
     # -- pieces -------------------------------------------------------------------------------------------
+    def _flatten(self, pgm, dev):
+        return Flat(pgm.to(dev).named_parameters(), dev)
+
     def _entry(self, key, B, table, index):
         ent = self._statics.get(key)
         if ent is None:
@@ -190,8 +171,7 @@ class PgmTrainStep:
     def _static_from(self, table, index):
         if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != self.ncol or not table.is_contiguous() or table.device.type != "cuda":
             raise ValueError(f"PgmTrainStep.step_from: the table must be a contiguous f32 [N, {self.ncol}] device tensor")
-        if index.dtype != torch.int64 or index.dim() != 1 or index.device.type != "cuda":
-            raise ValueError("PgmTrainStep.step_from: the index must be a device int64 vector")
+        check_index(index, "PgmTrainStep.step_from")
         B = int(index.numel())
         key = ("from", table.data_ptr(), int(table.shape[0]), B)
         ent = self._statics.get(key)
@@ -206,35 +186,12 @@ class PgmTrainStep:
                 ent["terms"].data_ptr(), self.out3.data_ptr() + 4)
 
     def _fwd_bwd(self, ent):
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        self.lib.pgm_nll_fwd_bwd(*self._launch_args(ent), ent["coef"].data_ptr(), ent["ws"].data_ptr(), ent["ws"].numel() * 4, st)
+        self.lib.pgm_nll_fwd_bwd(*self._launch_args(ent), ent["coef"].data_ptr(), ent["ws"].data_ptr(), ent["ws"].numel() * 4, self._stream())
         torch.div(self.out3[1:2], -float(ent["B"]), out=self.res[0:1])
 
     def _fwd(self, ent):
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        self.lib.pgm_nll_fwd(*self._launch_args(ent), st)
+        self.lib.pgm_nll_fwd(*self._launch_args(ent), self._stream())
         torch.div(self.out3[1:2], -float(ent["B"]), out=self.res[0:1])
-
-    def _optim(self):
-        self.tail.run(self.hp, self._on.flat_p, self.flat_g, self._ema.flat_p if self.ema_model is not None else None, self.out3,
-                      torch.cuda.current_stream(self.device).cuda_stream)
-        self.res[1:2].copy_(self.state[NORM:NORM + 1])
-
-    def _fwd_bwd_optim(self, ent):
-        self._fwd_bwd(ent)
-        self._optim()
-
-    def _run(self, key, ent):
-        self.it += 1
-        graph = self._graphs.get(key) if self.use_graph else None
-        if graph is not None:
-            graph.replay()
-        else:
-            self._fwd_bwd_optim(ent)
-            if self.use_graph:
-                self._graphs[key], _ = capture(lambda: self._fwd_bwd_optim(ent))
-        out = self.res.clone()
-        return {"loss": out[0], "grad_norm": out[1]}
 
     # -- public -------------------------------------------------------------------------------------------
     def step(self, **obs):
@@ -263,25 +220,12 @@ class PgmTrainStep:
         """(mean loss, {parameter name: d loss / d parameter}) of a batch; changes no parameter."""
         _, ent = self._static_for(obs)
         self._fwd_bwd(ent)
-        on = self._on
-        return self.res[0].clone(), {n: self.flat_g[o:o + p.numel()].view(p.shape).clone() for n, p, o in zip(on.names, on.params, on.p_off)}
+        return self.res[0].clone(), self._grads()
 
-    def state_dict(self):
-        """The reference checkpoint's keys (train_pgm.py:536-545): ``model_state_dict`` / ``ema_model_state_dict`` with the
-        reference's parameter names (``load_reference_state_dict`` takes either), ``optimizer_state_dict`` (flat AdamW moments in
-        ``named_parameters`` order, and the device step state)."""
-        sd = {"step": self.it, "model_state_dict": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-              "optimizer_state_dict": self.tail.flat_optimizer_state(self._on.names)}
-        if self.ema_model is not None:
-            sd["ema_model_state_dict"] = {k: v.detach().clone() for k, v in self.ema_model.state_dict().items()}
-        return sd
+    # -- checkpoint: also a reference checkpoint, whose ``encoder_*`` keys are dropped (``load_reference_state_dict``) -------------
+    def _load_model(self, model, sd):
+        model.load_reference_state_dict(sd)
 
-    def load_state_dict(self, sd):
-        """Also takes a reference checkpoint: its ``encoder_*`` keys are dropped, an absent optimiser state leaves the moments."""
-        self.model.load_reference_state_dict(sd["model_state_dict"])  # (copies in place: the flat views stay)
-        if self.ema_model is not None and "ema_model_state_dict" in sd:
-            self.ema_model.load_reference_state_dict(sd["ema_model_state_dict"])
-        opt = sd.get("optimizer_state_dict")
-        if opt is not None and "exp_avg" in opt:
-            self.tail.load_flat_optimizer_state(opt, self._on.names)
-        self.it = int(sd.get("step", 0))
+    def _optimizer_state(self, sd):
+        opt = sd.get("optimizer_state_dict")  # (absent, or torch's own layout, in a reference checkpoint: the moments stay)
+        return opt if opt is not None and "exp_avg" in opt else None

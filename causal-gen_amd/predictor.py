@@ -142,27 +142,33 @@ def _layered() -> bool:
     return os.environ.get("CGEN_PREDICTOR_LAYERED", "0") == "1"
 
 
+def fill_head(r, hd, xshape, std_fixed, ctx_width=None):
+    """Geometry and likelihood fields of the ``PredHead`` `r` for head `hd` on images of `xshape` ([B, C, R, R]), refusing another
+    input shape than the head was built for.  `ctx_width`: the columns of the context buffer the caller points ``y`` at (None: it
+    reads no context); the weight and ``y`` / ``obs`` pointers are the caller's."""
+    cnn = hd.cnn
+    if tuple(cnn.in_shape) != tuple(xshape[1:]):
+        raise ValueError(f"predictor head for {hd.var}: built for input {cnn.in_shape}, got {tuple(xshape[1:])}")
+    if ctx_width is not None and ctx_width != cnn.context_dim:
+        raise ValueError(f"predictor head for {hd.var}: context {hd.ctx_var} has {ctx_width} columns, expected {cnn.context_dim}")
+    r.c, r.res, r.width, r.nout, r.ctx = xshape[1], xshape[-1], cnn.width, cnn.num_outputs, cnn.context_dim
+    r.kind, r.tanh_loc, r.std_fixed = hd.kind, int(hd.tanh_loc), float(std_fixed)
+
+
 def _records(heads, obs, std_fixed, need_obs, need_ctx=True):
     """ctypes head records + the tensors they point into (kept alive by the caller)."""
     x = obs["x"]
-    B, C, R = x.shape[0], x.shape[1], x.shape[-1]
-    dev = x.device
+    B, dev = x.shape[0], x.device
     recs = (_lib.PredHead * len(heads))()
     keep = []
     for r, hd in zip(recs, heads):
-        cnn = hd.cnn
-        if tuple(cnn.in_shape) != (C, R, x.shape[-2]):
-            raise ValueError(f"predictor head for {hd.var}: built for input {cnn.in_shape}, got {tuple(x.shape[1:])}")
-        wb = cnn.folded(dev)
+        y = _col(obs[hd.ctx_var], B, dev) if hd.cnn.context_dim and need_ctx else None
+        fill_head(r, hd, x.shape, std_fixed, None if y is None else y.shape[1])
+        wb = hd.cnn.folded(dev)
         keep.append(wb)  # the records hold raw pointers into these: a refold between forward and backward must not free them
-        r.c, r.res, r.width, r.nout, r.ctx = C, R, cnn.width, cnn.num_outputs, cnn.context_dim
-        r.kind, r.tanh_loc, r.std_fixed = hd.kind, int(hd.tanh_loc), float(std_fixed)
         for i, (w, b) in enumerate(wb):
             r.w[i], r.b[i] = w.data_ptr(), b.data_ptr()
-        if cnn.context_dim and need_ctx:
-            y = _col(obs[hd.ctx_var], B, dev)
-            if y.shape[1] != cnn.context_dim:
-                raise ValueError(f"predictor head for {hd.var}: context {hd.ctx_var} has {y.shape[1]} columns, expected {cnn.context_dim}")
+        if y is not None:
             keep.append(y)
             r.y = y.data_ptr()
         if need_obs:

@@ -6,7 +6,8 @@
     global grad-norm -> clip at ``grad_clip`` / NaN-loss skip (on device) -> fused AdamW + EMA -> step counter commit
 
 ``loss`` is ``model_anticausal``'s summed negative log-likelihood of the four heads divided by the batch size; the optimiser is
-the reference's ``AdamW`` under ``LambdaLR(linear_warmup)`` with ``clip_grad_norm_`` and ``EMA`` (``step_tail.StepTail``).  No host
+the reference's ``AdamW`` under ``LambdaLR(linear_warmup)`` with ``clip_grad_norm_`` and ``EMA`` (``step_tail.StepTail``; the
+skeleton around it, the staging of ``step`` and the data-set half of ``step_from`` are ``step_tail.ImageSupStep``'s).  No host
 synchronisation inside a step; the whole step is captured into one hipGraph after an eager first step.
 
 The 68 distinct parameters (60 of the ONE trunk, then the four ``fc`` pairs, in ``named_parameters()`` order) live in one flat f32
@@ -18,7 +19,6 @@ once, with one mask.
 ``ChestPredictor`` itself is unchanged: its ``train()`` still leaves eval mode on, ``_heads()`` still raises, and every eval route
 sees the trained weights because the step drops the predictor's cached weight images after it has written the parameters.
 """
-import copy
 import ctypes as C
 
 import torch
@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from .predictor import _prep_x
 from .predictor_resnet import MAX_RES, MIN_RES, _VARS, ChestPredictor, _conv_sites
-from .step_tail import NORM, Flat, HyperParams, StepTail, capture, check_warmup
+from .step_tail import Flat, ImageSupStep
 
 N_PARAMS = 68  # 20 convs, 20 GroupNorm pairs, 4 Linear pairs
 
@@ -54,51 +54,47 @@ class _Flat(Flat):
         self.pred.__dict__.pop("_rt", None)
 
 
-class ChestPredictorTrainStep:
+class ChestPredictorTrainStep(ImageSupStep):
+    """``state_dict()`` holds all 248 ``encoder_*`` names, the optimiser state in ``named_parameters()`` order, and the Philox state
+    (``rng_state``)."""
     NORM_BLOCKS = 1024
 
     def __init__(self, pred, lr=1e-4, wd=0.1, betas=(0.9, 0.999), eps=1e-8, grad_clip=200.0, lr_warmup_steps=1, ema_rate=0.999,
                  ema=True, ema_update_after=100, use_graph=True, p_dropout=0.2, device="cuda", columns=None):
-        check_warmup(lr_warmup_steps)
         if not isinstance(pred, ChestPredictor):
             raise TypeError("ChestPredictorTrainStep trains a predictor_resnet.ChestPredictor; the CNN predictors are PredictorTrainStep's")
         if not 0.0 <= float(p_dropout) < 1.0:
             raise ValueError(f"p_dropout must lie in [0, 1), got {p_dropout}")
         if pred.input_channels != 1:
             raise ValueError(f"ChestPredictorTrainStep: input_channels must be 1, got {pred.input_channels}")
-        self.lib = _lib.require_gpu()
-        dev = self.device = torch.device(device)
-        # (no norm threshold in sup_epoch: only a non-finite norm or a NaN loss drops the step)
-        self.hp = HyperParams(float(lr), (float(betas[0]), float(betas[1])), float(eps), float(wd), float(grad_clip), float("inf"),
-                              int(lr_warmup_steps), float(ema_rate), int(ema_update_after))
-        self.use_graph, self.p_dropout = use_graph, float(p_dropout)
-        # {variable: column of ds.pa, or (first column, width)} for step_from (cf_eval.predictor_eval's convention)
-        self.columns = None if columns is None else {k: (int(v), 1) if isinstance(v, int) else (int(v[0]), int(v[1])) for k, v in columns.items()}
-        self.ema_model = None
-        if ema:
-            self.ema_model = copy.deepcopy(pred)
-            self.ema_model.requires_grad_(False)
-            self._ema = _Flat(self.ema_model, dev)
-        self.model = pred
-        self._on = _Flat(pred, dev)
-        n = self._on.flat_p.numel()
-        self.flat_g = torch.zeros(n, device=dev)
-        self.tail = StepTail(self.lib, n, dev, self.NORM_BLOCKS)
-        self.stats = self.tail.stats  # host read of the device-side step state (one sync)
-        self.m, self.v, self.state, self.partial = self.tail.m, self.tail.v, self.tail.state, self.tail.partial
-        self.out3 = torch.zeros(3, device=dev)  # [-, summed loss, 0]: what cgen_clip_decide tests for NaN
-        self.res = torch.zeros(2, device=dev)   # [mean loss, gradient norm] of the last step
+        super().__init__(pred, columns, lr=lr, wd=wd, betas=betas, eps=eps, grad_clip=grad_clip, lr_warmup_steps=lr_warmup_steps,
+                         ema_rate=ema_rate, ema=ema, use_graph=use_graph, ema_update_after=ema_update_after, device=device)
+        self.p_dropout = float(p_dropout)
         # Philox state {seed, offset} of Dropout and of step_from's crop / flip draws (different streams of one state)
-        self._rng = torch.tensor([torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, 0], dtype=torch.int64, device=dev)
-        self._statics, self._graphs = {}, {}
-        self._last = None  # (B, R) of the last forward
-        self.it = 0
+        self._rng = self._new_rng()
+        self._last = None  # the entry of the last forward
 
     # -- pieces -------------------------------------------------------------------------------------------
-    def _build(self, B, R, x, at):
+    def _flatten(self, pred, dev):
+        return _Flat(pred, dev)
+
+    def _variables(self):
+        return _VARS
+
+    def _check_batch(self, B):
+        if B < 1:
+            raise ValueError("ChestPredictorTrainStep.step_from: an empty index")
+
+    def _check_geometry(self, ds, r_h, r_w):
+        if ds.c != 1:
+            raise ValueError(f"ChestPredictorTrainStep.step_from: the data set has {ds.c} channels, the predictor reads 1")
+        if r_h != r_w:
+            raise ValueError(f"ChestPredictorTrainStep.step_from: the crop is {r_h} x {r_w}, the predictor reads square images")
+
+    def _build(self, x, at, dense):
         """Argument record, workspace and coefficient of a batch shape reading the static image `x`.  ``at(var)`` = (address, row
-        stride in floats, width) of a variable's rows."""
-        dev, on, pred = self.device, self._on, self.model
+        stride in floats, width) of a variable's rows (``finding`` is read where it lies: no `dense` copy)."""
+        dev, on, pred, B, R = self.device, self._on, self.model, int(x.shape[0]), int(x.shape[-1])
         if R != pred.input_res or not MIN_RES <= R <= MAX_RES:
             raise ValueError(f"ChestPredictorTrainStep: built for square images of input_res {pred.input_res} within {MIN_RES}..{MAX_RES}, got {R}")
         g_of = {id(p): self.flat_g.data_ptr() + 4 * o for p, o in zip(on.params, on.p_off)}
@@ -124,72 +120,14 @@ class ChestPredictorTrainStep:
                     coef=torch.full((1,), 1.0 / B, device=dev))
 
     def _static_for(self, obs):
-        """Static input buffers, argument record and workspace of a batch shape; `obs` is copied into the buffers."""
         x = _prep_x(obs["x"])
         if x.dim() != 4 or x.shape[0] < 1 or x.shape[1] != 1 or x.shape[-1] != x.shape[-2]:
             raise ValueError(f"ChestPredictorTrainStep: needs x of [B >= 1, 1, R, R], got {tuple(x.shape)}")
-        B, R = int(x.shape[0]), int(x.shape[-1])
-        cols = {}
-        for var in _VARS:
-            if var not in obs:
-                raise KeyError(f"ChestPredictorTrainStep: observation {var!r} is missing")
-            cols[var] = obs[var].detach().reshape(B, -1).float()
-        key = tuple(x.shape)
-        ent = self._statics.get(key)
-        if ent is None:
-            sc = {k: torch.empty(v.shape, device=self.device) for k, v in cols.items()}
-            xs = torch.empty_like(x, device=self.device)
-            ent = self._statics[key] = self._build(B, R, xs, lambda var: (sc[var].data_ptr(), sc[var].shape[1], sc[var].shape[1]))
-            ent["cols"] = sc
-        ent["x"].copy_(x, non_blocking=True)  # (device to device: _prep_x has moved the image)
-        for k, v in cols.items():
-            if v.shape != ent["cols"][k].shape:
-                raise ValueError(f"ChestPredictorTrainStep: observation {k!r} changed shape from {tuple(ent['cols'][k].shape)} to {tuple(v.shape)}")
-            # a host column may be a temporary: only a copy that has finished may let go of it
-            ent["cols"][k].copy_(v, non_blocking=v.is_cuda)
-        return key, ent
-
-    def _static_from(self, ds, index, train, draws_out):
-        """Static image, parents rows and index of a (data set, batch size): the record points into the gathered parents rows."""
-        if self.columns is None:
-            raise ValueError("ChestPredictorTrainStep.step_from: name the columns of ds.pa at construction (columns={variable: column})")
-        missing = [v for v in _VARS if v not in self.columns]
-        if missing:
-            raise ValueError(f"ChestPredictorTrainStep.step_from: no column was named for {missing}")
-        if index.dtype != torch.int64 or index.dim() != 1 or index.device.type != "cuda":
-            raise ValueError("ChestPredictorTrainStep.step_from: the index must be a device int64 vector")
-        B = int(index.numel())
-        if B < 1:
-            raise ValueError("ChestPredictorTrainStep.step_from: an empty index")
-        if draws_out is not None:
-            assert draws_out.dtype == torch.int32 and tuple(draws_out.shape) == (B, 3) and draws_out.is_contiguous() and draws_out.is_cuda
-        key = (ds.key(train), B, None if draws_out is None else draws_out.data_ptr())
-        ent = self._statics.get(key)
-        if ent is None:
-            dev = self.device
-            if ds.c != 1:
-                raise ValueError(f"ChestPredictorTrainStep.step_from: the data set has {ds.c} channels, the predictor reads 1")
-            for var in _VARS:
-                c0, k = self.columns[var]
-                if not 0 <= c0 <= ds.ctx - k:
-                    raise ValueError(f"ChestPredictorTrainStep.step_from: variable {var!r}: columns {c0}..{c0 + k - 1} do not fit ds.pa's {ds.ctx}")
-            r_h, r_w, _, _, _ = ds.geometry(train)
-            if r_h != r_w:
-                raise ValueError(f"ChestPredictorTrainStep.step_from: the crop is {r_h} x {r_w}, the predictor reads square images")
-            x = torch.empty((B, 1, r_h, r_w), device=dev)
-            pa = torch.zeros((B, ds.ctx), device=dev)
-            ent = self._statics[key] = self._build(B, r_h, x, lambda var: (pa.data_ptr() + 4 * self.columns[var][0], ds.ctx, self.columns[var][1]))
-            view = _lib.View(x.data_ptr(), r_h * r_w, r_w, 1, 1, 0)  # one channel: NHWC and NCHW are the same memory
-            index_buf = torch.zeros(B, dtype=torch.int64, device=dev)
-            args = ds.args_for(_lib.F32, B, index_buf.data_ptr(), view, self._rng.data_ptr(), train, None,
-                               None if draws_out is None else draws_out.data_ptr(), pa.data_ptr())
-            ent.update(pa=pa, index=index_buf, aug=args, keep=(ds, draws_out))
-        ent["index"].copy_(index, non_blocking=True)
-        return key, ent
+        return self._stage(x, obs)
 
     def _fwd_bwd(self, ent, dx=None):
         """Philox state + 1, [augment], the weight images, the training forward and every gradient of loss / B"""
-        st = torch.cuda.current_stream(self.device).cuda_stream
+        st = self._stream()
         lib, a, B, ws, t = self.lib, ent["args"], ent["B"], ent["ws"], self._on.tables
         lib.rng_advance(self._rng.data_ptr(), 1, st)
         if "aug" in ent:
@@ -201,34 +139,9 @@ class ChestPredictorTrainStep:
                              None if dx is None else dx.data_ptr(), st)
         torch.mul(self.out3[1:2], 1.0 / B, out=self.res[0:1])
 
-    def _optim(self):
-        ema = self.ema_model is not None
-        self.tail.run(self.hp, self._on.flat_p, self.flat_g, self._ema.flat_p if ema else None, self.out3,
-                      torch.cuda.current_stream(self.device).cuda_stream)
-        self.res[1:2].copy_(self.state[NORM:NORM + 1])
-
-    def _fwd_bwd_optim(self, ent):
-        self._fwd_bwd(ent)
-        self._optim()
-
-    def _invalidate(self):
-        self._on.invalidate()
-        if self.ema_model is not None:
-            self._ema.invalidate()
-
     def _run(self, key, ent):
-        self.it += 1
         self._last = ent
-        graph = self._graphs.get(key) if self.use_graph else None
-        if graph is not None:
-            graph.replay()
-        else:
-            self._fwd_bwd_optim(ent)
-            if self.use_graph:
-                self._graphs[key], _ = capture(lambda: self._fwd_bwd_optim(ent))
-        self._invalidate()
-        out = self.res.clone()
-        return {"loss": out[0], "grad_norm": out[1]}
+        return super()._run(key, ent)
 
     # -- public -------------------------------------------------------------------------------------------
     def step(self, **obs):
@@ -250,8 +163,7 @@ class ChestPredictorTrainStep:
         gx = torch.empty_like(ent["x"]) if dx else None
         self._last = ent
         self._fwd_bwd(ent, gx)
-        on = self._on
-        grads = {n: self.flat_g[o:o + p.numel()].view(p.shape).clone() for n, p, o in zip(on.names, on.params, on.p_off)}
+        grads = self._grads()
         if dx:
             grads["x"] = gx
         return self.res[0].clone(), grads
@@ -288,22 +200,9 @@ class ChestPredictorTrainStep:
         """{batch key: bytes of its workspace}"""
         return {k: 4 * e["ws"].numel() for k, e in self._statics.items()}
 
-    def state_dict(self):
-        """The reference checkpoint's keys (train_pgm.py:536-545): ``model_state_dict`` / ``ema_model_state_dict`` with all 248
-        ``encoder_*`` names, ``optimizer_state_dict`` (flat AdamW moments in ``named_parameters()`` order and the device step
-        state), and the Philox state."""
-        sd = {"step": self.it, "model_state_dict": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
-              "optimizer_state_dict": self.tail.flat_optimizer_state(self._on.names), "rng_state": self._rng.clone()}
-        if self.ema_model is not None:
-            sd["ema_model_state_dict"] = {k: v.detach().clone() for k, v in self.ema_model.state_dict().items()}
-        return sd
+    def _extra_state(self):
+        return {"rng_state": self._rng.clone()}
 
-    def load_state_dict(self, sd):
-        self.model.load_state_dict(sd["model_state_dict"], strict=True)  # (copies in place: the flat views stay)
-        if self.ema_model is not None and "ema_model_state_dict" in sd:
-            self.ema_model.load_state_dict(sd["ema_model_state_dict"], strict=True)
-        self.tail.load_flat_optimizer_state(sd["optimizer_state_dict"], self._on.names)
+    def _load_extra_state(self, sd):
         if "rng_state" in sd:
             self._rng.copy_(sd["rng_state"])
-        self.it = int(sd.get("step", 0))
-        self._invalidate()

@@ -1,8 +1,17 @@
-"""What the device-side training steps (``train.TrainStep``, ``predictor_train.PredictorTrainStep``, ``pgm_train.PgmTrainStep``)
-have in common: the optimiser tail of csrc/optim.hip as one launch sequence (``StepTail``), the names of its state vector, the
-eager-first-then-capture helper, and the flattening of a module's parameters into one f32 buffer.  A step owns its forward and
-backward pass, its graph keys and its data-parallel exchange; everything after the gradient is here.
+"""What the device-side training steps (``train.TrainStep``, ``cf_train.CfTrainStep``, ``predictor_train.PredictorTrainStep``,
+``predictor_resnet_train.ChestPredictorTrainStep``, ``pgm_train.PgmTrainStep``) have in common: the optimiser tail of csrc/optim.hip
+as one launch sequence (``StepTail``), the names of its state vector, the eager-first-then-capture helper, and the flattening of a
+module's parameters into one f32 buffer.  A step owns its forward and backward pass, its graph keys and its data-parallel exchange;
+everything after the gradient is here.
+
+The three supervised steps (stages one and two of the pipeline) share more than the tail, and that is here too: ``SupStep`` is
+their skeleton -- hyper-parameters, EMA copy, the two ``Flat``s, gradient buffer and tail, ``_optim``, the eager-first-then-replay
+``_run``, the gradient dictionary and the checkpoint pair; a subclass brings ``_flatten``, ``_fwd_bwd`` and its static entries.
+``ImageSupStep`` adds what the two image steps share: the staging of observation columns for ``step`` and the data-set half of
+``step_from``.  ``TrainStep`` and ``CfTrainStep`` are driven by the engine, key their graphs differently and return other things:
+they use the tail and the helpers, not the skeleton.
 """
+import copy
 import ctypes as C
 from collections import namedtuple
 
@@ -27,6 +36,17 @@ def check_warmup(n):
         raise ValueError(f"lr_warmup_steps must be > 0 (got {n}): the linear warm-up divides by it")
 
 
+def normalize_columns(columns):
+    """``columns=`` of a step's ``step_from``: {variable: column of ds.pa, or (first column, width)} as {variable: (first column,
+    width)} (cf_eval.predictor_eval's convention); None stays None."""
+    return None if columns is None else {k: (int(v), 1) if isinstance(v, int) else (int(v[0]), int(v[1])) for k, v in columns.items()}
+
+
+def check_index(index, who):
+    if index.dtype != torch.int64 or index.dim() != 1 or index.device.type != "cuda":
+        raise ValueError(f"{who}: the index must be a device int64 vector")
+
+
 def flatten(tensors, dev):
     """One f32 buffer holding `tensors` back to back; each tensor's ``.data`` becomes a view of it.  Returns (flat, offsets)."""
     flat = torch.empty(sum(t.numel() for t in tensors), dtype=torch.float32, device=dev)
@@ -47,6 +67,9 @@ class Flat:
         named = list(named)
         self.names, self.params = [n for n, _ in named], [p for _, p in named]
         self.flat_p, self.p_off = flatten(self.params, dev)
+
+    def invalidate(self):
+        """After the kernels have written the parameters through raw pointers: drop what the owner cached of their old values."""
 
 
 def ranges_where(eng, pred):
@@ -173,3 +196,197 @@ class StepTail:
         self.m.copy_(sd["exp_avg"])
         self.v.copy_(sd["exp_avg_sq"])
         self.state.copy_(sd["state"])
+
+
+class SupStep:
+    """The skeleton of a supervised training step: one model, its EMA copy, one flat gradient and the tail, run eagerly once per
+    static entry and replayed from a hipGraph afterwards.  A subclass gives ``NORM_BLOCKS``, ``_flatten(model, dev)`` (the ``Flat``
+    of a model; called for the EMA copy first, the online model second) and ``_fwd_bwd(ent)`` (every launch up to the gradient
+    of loss / B in ``flat_g``, the summed loss in ``out3[1]`` and the mean loss in ``res[0]``), and may override ``_ema_only``
+    and the four checkpoint hooks below ``state_dict``."""
+
+    def __init__(self, model, lr, wd, betas, eps, grad_clip, lr_warmup_steps, ema_rate, ema, use_graph, ema_update_after, device):
+        check_warmup(lr_warmup_steps)
+        self.lib = _lib.require_gpu()
+        dev = self.device = torch.device(device)
+        # (no norm threshold in sup_epoch: only a non-finite norm or a NaN loss drops the step)
+        self.hp = HyperParams(float(lr), (float(betas[0]), float(betas[1])), float(eps), float(wd), float(grad_clip), float("inf"),
+                              int(lr_warmup_steps), float(ema_rate), int(ema_update_after))
+        self.use_graph = use_graph
+        self.ema_model = self._ema = None
+        if ema:
+            self.ema_model = copy.deepcopy(model)
+            self.ema_model.requires_grad_(False)
+            self._ema = self._flatten(self.ema_model, dev)
+        self.model = model
+        self._on = self._flatten(model, dev)
+        n = self._on.flat_p.numel()
+        self.flat_g = torch.zeros(n, device=dev)
+        self.tail = StepTail(self.lib, n, dev, self.NORM_BLOCKS)
+        self.stats = self.tail.stats  # host read of the device-side step state (one sync)
+        self.m, self.v, self.state, self.partial = self.tail.m, self.tail.v, self.tail.state, self.tail.partial
+        self.out3 = torch.zeros(3, device=dev)  # [-, summed loss (PgmTrainStep: log-probability), 0]: what cgen_clip_decide tests for NaN
+        self.res = torch.zeros(2, device=dev)   # [mean loss, gradient norm] of the last step
+        self._statics, self._graphs = {}, {}
+        self.it = 0
+
+    # -- pieces -------------------------------------------------------------------------------------------
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _ema_only(self):
+        """(p_ptr, ema_ptr, count) regions that are averaged into the EMA copy and otherwise left alone (``StepTail.run``)"""
+        return ()
+
+    def _optim(self):
+        self.tail.run(self.hp, self._on.flat_p, self.flat_g, None if self._ema is None else self._ema.flat_p, self.out3, self._stream(),
+                      ema_only=self._ema_only())
+        self.res[1:2].copy_(self.state[NORM:NORM + 1])
+
+    def _fwd_bwd_optim(self, ent):
+        self._fwd_bwd(ent)
+        self._optim()
+
+    def _invalidate(self):
+        self._on.invalidate()
+        if self._ema is not None:
+            self._ema.invalidate()
+
+    def _run(self, key, ent):
+        self.it += 1
+        graph = self._graphs.get(key) if self.use_graph else None
+        if graph is not None:
+            graph.replay()
+        else:
+            self._fwd_bwd_optim(ent)
+            if self.use_graph:
+                self._graphs[key], _ = capture(lambda: self._fwd_bwd_optim(ent))
+        self._invalidate()
+        out = self.res.clone()
+        return {"loss": out[0], "grad_norm": out[1]}
+
+    def _grads(self):
+        """{parameter name: a copy of its part of the flat gradient}"""
+        on = self._on
+        return {n: self.flat_g[o:o + p.numel()].view(p.shape).clone() for n, p, o in zip(on.names, on.params, on.p_off)}
+
+    # -- checkpoint ---------------------------------------------------------------------------------------
+    def state_dict(self):
+        """The reference checkpoint's keys (train_pgm.py:536-545): ``model_state_dict`` / ``ema_model_state_dict`` with the
+        reference's parameter names, ``optimizer_state_dict`` (flat AdamW moments in the order of ``_on.names`` and the device
+        step state), and what ``_extra_state`` adds."""
+        sd = {"step": self.it, "model_state_dict": {k: v.detach().clone() for k, v in self.model.state_dict().items()},
+              "optimizer_state_dict": self.tail.flat_optimizer_state(self._on.names), **self._extra_state()}
+        if self.ema_model is not None:
+            sd["ema_model_state_dict"] = {k: v.detach().clone() for k, v in self.ema_model.state_dict().items()}
+        return sd
+
+    def load_state_dict(self, sd):
+        self._load_model(self.model, sd["model_state_dict"])  # (copies in place: the flat views stay)
+        if self.ema_model is not None and "ema_model_state_dict" in sd:
+            self._load_model(self.ema_model, sd["ema_model_state_dict"])
+        opt = self._optimizer_state(sd)
+        if opt is not None:
+            self.tail.load_flat_optimizer_state(opt, self._on.names)
+        self._load_extra_state(sd)
+        self.it = int(sd.get("step", 0))
+        self._invalidate()
+
+    def _extra_state(self):
+        return {}
+
+    def _load_extra_state(self, sd):
+        pass
+
+    def _load_model(self, model, sd):
+        model.load_state_dict(sd, strict=True)
+
+    def _optimizer_state(self, sd):
+        """The optimiser state to load, or None to leave the moments (here: a checkpoint without one is an error)"""
+        return sd["optimizer_state_dict"]
+
+
+class ImageSupStep(SupStep):
+    """What the two anticausal-predictor steps share on top: ``columns=``, the staging of a batch given by variable (``step``) and
+    the data-set half of ``step_from``.  A subclass gives ``_variables()`` (every variable it reads), ``_check_batch(B)``,
+    ``_build(x, at, dense)`` (the static entry of a batch shape reading the static image `x`; it holds ``x``) and may refuse a
+    data set's geometry in ``_check_geometry``."""
+
+    def __init__(self, model, columns, **kw):
+        # {variable: (first column of ds.pa, width)} for step_from
+        self.columns = normalize_columns(columns)
+        super().__init__(model, **kw)
+
+    def _new_rng(self):
+        """A Philox state {seed, offset} of the step's own, seeded from ``torch.initial_seed()``"""
+        return torch.tensor([torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, 0], dtype=torch.int64, device=self.device)
+
+    def _cols(self, obs, B):
+        """{variable: [B, k] f32} of every observed / context variable the step reads"""
+        out = {}
+        for var in self._variables():
+            if var not in obs:
+                raise KeyError(f"{type(self).__name__}: observation {var!r} is missing")
+            out[var] = obs[var].detach().reshape(B, -1).float()
+        return out
+
+    def _check_geometry(self, ds, r_h, r_w):
+        pass
+
+    def _stage(self, x, obs):
+        """(key, entry) of a batch shape for ``step``: static input buffers and what ``_build`` makes of them; the prepared image
+        `x` and the columns of `obs` are copied into the buffers."""
+        name, cols = type(self).__name__, self._cols(obs, int(x.shape[0]))
+        key = tuple(x.shape)
+        ent = self._statics.get(key)
+        if ent is None:
+            sc = {k: torch.empty(v.shape, device=self.device) for k, v in cols.items()}
+            at = lambda var: (sc[var].data_ptr(), sc[var].shape[1], sc[var].shape[1])  # noqa: E731
+            ent = self._statics[key] = self._build(torch.empty_like(x, device=self.device), at, sc)
+            ent["cols"] = sc
+        ent["x"].copy_(x, non_blocking=True)  # (device to device: _prep_x has moved the image)
+        for k, v in cols.items():
+            if v.shape != ent["cols"][k].shape:
+                raise ValueError(f"{name}: observation {k!r} changed shape from {tuple(ent['cols'][k].shape)} to {tuple(v.shape)}")
+            # a host column may be a temporary of _cols: only a copy that has finished may let go of it
+            ent["cols"][k].copy_(v, non_blocking=v.is_cuda)
+        return key, ent
+
+    def _static_from(self, ds, index, train, draws_out):
+        """(key, entry) of a (data set, batch size): static image, gathered parents rows ``pa`` and index, and the augment launch's
+        arguments ``aug``.  ``_build``'s ``at(var)`` points into the parents rows (no `dense` buffers: a subclass that needs a
+        contiguous copy of a variable makes it inside the step)."""
+        who = f"{type(self).__name__}.step_from"
+        if self.columns is None:
+            raise ValueError(f"{who}: name the columns of ds.pa at construction (columns={{variable: column}})")
+        missing = [v for v in self._variables() if v not in self.columns]
+        if missing:
+            raise ValueError(f"{who}: no column was named for {missing}")
+        check_index(index, who)
+        B = int(index.numel())
+        self._check_batch(B)
+        if draws_out is not None:
+            assert draws_out.dtype == torch.int32 and tuple(draws_out.shape) == (B, 3) and draws_out.is_contiguous() and draws_out.is_cuda
+        key = (ds.key(train), B, None if draws_out is None else draws_out.data_ptr())
+        ent = self._statics.get(key)
+        if ent is None:
+            dev = self.device
+            for var in self._variables():
+                c0, k = self.columns[var]
+                if not 0 <= c0 <= ds.ctx - k:
+                    raise ValueError(f"{who}: variable {var!r}: columns {c0}..{c0 + k - 1} do not fit ds.pa's {ds.ctx}")
+            r_h, r_w, _, _, _ = ds.geometry(train)
+            self._check_geometry(ds, r_h, r_w)
+            x = torch.empty((B, ds.c, r_h, r_w), device=dev)
+            pa = torch.zeros((B, ds.ctx), device=dev)
+            ent = self._statics[key] = self._build(x, lambda var: (pa.data_ptr() + 4 * self.columns[var][0], ds.ctx, self.columns[var][1]), None)
+            if self._rng is None:
+                self._rng = self._new_rng()
+            # one channel: NHWC and planar are the same memory and the existing launch serves; else the planar one
+            view = _lib.View(x.data_ptr(), r_h * r_w, r_w, 1, 1, 0) if ds.c == 1 else ds.planar_view(x.data_ptr(), train)
+            index_buf = torch.zeros(B, dtype=torch.int64, device=dev)
+            args = ds.args_for(_lib.F32, B, index_buf.data_ptr(), view, self._rng.data_ptr(), train, None,
+                               None if draws_out is None else draws_out.data_ptr(), pa.data_ptr())
+            ent.update(pa=pa, index=index_buf, aug=args, train=train, keep=(ds, draws_out))
+        ent["index"].copy_(index, non_blocking=True)
+        return key, ent
