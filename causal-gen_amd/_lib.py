@@ -237,6 +237,7 @@ PROTOTYPES = {
     "cgen_block4_pair_supported": [C.POINTER(Block4Args), C.POINTER(Block4Args)],
     "cgen_block4_pair": [C.POINTER(Block4Args), C.POINTER(Block4Args), vp],
     "cgen_conv2d_wgrad_plan": [C.POINTER(WgradArgs), C.POINTER(i32)],
+    "cgen_conv2d_wgrad_plan_record": [C.POINTER(WgradArgs), C.POINTER(i32)],
     "cgen_conv2d_wgrad_batch_plan": [vp, i32, vp, i64, vp, vp, i32, vp, vp],
     "cgen_conv2d_wgrad_batch_run": [vp, vp, i32, i32, vp],
     "cgen_conv2d_wgrad": [C.POINTER(WgradArgs), vp],
@@ -342,7 +343,7 @@ PROTOTYPES = {
 }
 _RESTYPES = {"cgen_last_error": C.c_char_p, "cgen_conv2d_last_kernel": C.c_char_p}
 ABI_VERSION = 411  # CGEN_ABI_VERSION of include/cgen_hip.h this binding was written against
-_NOCHECK = {"cgen_version", "cgen_h16_format", "cgen_last_error", "cgen_conv2d_wgrad_plan", "cgen_reparam_kl_chunks", "cgen_like_chunks",
+_NOCHECK = {"cgen_version", "cgen_h16_format", "cgen_last_error", "cgen_conv2d_wgrad_plan", "cgen_conv2d_wgrad_plan_record", "cgen_reparam_kl_chunks", "cgen_like_chunks",
             "cgen_block3_supported", "cgen_block4_supported", "cgen_block4_pair_supported", "cgen_block4_plan", "cgen_block4_pair_plan", "cgen_block3_pair_supported", "cgen_block3_pair_plan", "cgen_block3_plan", "cgen_conv2d_pair_supported", "cgen_stem_conv_supported",
             "cgen_predictor_supported", "cgen_predictor_tiled_supported", "cgen_batch_augment_arm", "cgen_latent_tail_bwd_supported", "cgen_latent_tail_fwd_supported",
             "cgen_dgauss_head_supported", "cgen_conv2d_last_kernel"}

@@ -652,8 +652,7 @@ static void launch_wgrad2_ks(const Wg2P& p, const Wg2Geom& g, hipStream_t st) {
 }
 
 template <typename T>
-static int launch_wgrad(const WgP& p, hipStream_t st) {
-  const int ntc = wgrad_ntc(p.Co);
+static int launch_wgrad(const WgP& p, const int ntc, hipStream_t st) {
   dim3 grid(p.nsplit, p.n_cichunks, ceil_div(p.Co, ntc * 16) * p.n_tapgroups), block(256);
   if (ntc == 1) hipLaunchKernelGGL((wgrad_kernel<T, 1>), grid, block, 0, st, p);
   else if (ntc == 2) hipLaunchKernelGGL((wgrad_kernel<T, 2>), grid, block, 0, st, p);
@@ -695,28 +694,6 @@ static bool wgrad_tiled_ok(const cgen_wgrad_args* a, Wg2Geom& g) {
   for (int s = 0; s < a->nseg; ++s)
     if (!fits(a->seg[s])) return false;
   return wgrad2_geometry(a->n, a->h, a->w, a->gout.c, ctot8_of(segc, a->nseg), a->ks, g);
-}
-
-extern "C" int cgen_conv2d_wgrad_plan(const cgen_wgrad_args* a, int32_t* tiled_out) {
-  if (!a || a->nseg < 1 || a->nseg > CGEN_MAX_SEG) return 0;
-  {
-    Wg3Plan g3;
-    if (wg3_plan(a, g3)) {
-      if (tiled_out) *tiled_out = 2 + g3.q.layout;
-      return g3.nsplit_total;
-    }
-  }
-  Wg2Geom g;
-  if (wgrad_tiled_ok(a, g)) {
-    if (tiled_out) *tiled_out = 1;
-    return g.nsplit;
-  }
-  if (tiled_out) *tiled_out = 0;
-  int ci_total = 0;
-  for (int s = 0; s < a->nseg; ++s) ci_total += a->seg[s].c;
-  int nsplit, pps;
-  wgrad_geometry(a->n * a->h * a->w, a->gout.c, (ci_total + 31) / 32, a->ks, nsplit, pps);
-  return nsplit;
 }
 
 // Wg2P + geometry of one problem for the tiled bf16 kernel (false: not eligible, the caller uses the generic kernel)
@@ -928,12 +905,31 @@ extern "C" int cgen_conv2d_wgrad_batch_run(const void* blob_dev, const cgen_wgra
   return check_launch("cgen_conv2d_wgrad_batch_run");
 }
 
-extern "C" int cgen_conv2d_wgrad(const cgen_wgrad_args* a, cgen_stream_t stream) {
-  CGEN_REQUIRE(a && a->partial_w, "cgen_conv2d_wgrad: null args");
-  CGEN_REQUIRE(a->dtype == CGEN_F32 || a->dtype == CGEN_F16, "cgen_conv2d_wgrad: bad dtype");
-  CGEN_REQUIRE(a->nseg >= 1 && a->nseg <= CGEN_MAX_SEG && a->gout.p && a->gout.c > 0, "cgen_conv2d_wgrad: bad args");
-  const int esz = a->dtype == CGEN_F32 ? 4 : 2;
-  WgP p;
+// The launch decision, made ONCE per call: cgen_conv2d_wgrad launches from this record, cgen_conv2d_wgrad_plan and
+// cgen_conv2d_wgrad_plan_record report it.  Host code: nothing is dereferenced.
+struct WgradDecision {
+  int kind, nsplit;  // kind as cgen_conv2d_wgrad_plan names it: 0 generic, 1 tiled, 2 / 3 streaming (partial layout 0 / 1)
+  Wg3Plan g3;        // kinds 2, 3
+  Wg2P q2;           // kind 1
+  Wg2Geom g2;
+  WgP p;             // kind 0
+  int ntc, esz;
+};
+
+static void wgrad_decide(const cgen_wgrad_args* a, WgradDecision& d) {
+  if (wg3_plan(a, d.g3)) {  // streaming kernel of round 5 (csrc/wgrad3.hip) where it serves the shape
+    d.kind = 2 + d.g3.q.layout;
+    d.nsplit = d.g3.nsplit_total;
+    return;
+  }
+  if (build_wg2(a, d.q2, d.g2)) {  // tiled bf16 kernel when the shape allows it
+    d.kind = 1;
+    d.nsplit = d.g2.nsplit;
+    return;
+  }
+  d.kind = 0;
+  d.esz = a->dtype == CGEN_F32 ? 4 : 2;
+  WgP& p = d.p;
   memset(&p, 0, sizeof(p));
   p.N = a->n; p.H = a->h; p.W = a->w; p.KS = a->ks; p.pad = a->ks / 2; p.nseg = a->nseg; p.act = a->act;
   p.Co = a->gout.c; p.P = a->n * a->h * a->w; p.taps = a->ks * a->ks;
@@ -941,7 +937,7 @@ extern "C" int cgen_conv2d_wgrad(const cgen_wgrad_args* a, cgen_stream_t stream)
   for (int s = 0; s < a->nseg; ++s) {
     p.seg[s] = mk(a->seg[s]);
     p.seg_off[s] = off;
-    p.seg_vec[s] = vec16_ok(a->seg[s], esz);
+    p.seg_vec[s] = vec16_ok(a->seg[s], d.esz);
     p.seg_chunk0[s] = ch;
     off += a->seg[s].c;
     ch += (a->seg[s].c + 31) / 32;
@@ -950,44 +946,72 @@ extern "C" int cgen_conv2d_wgrad(const cgen_wgrad_args* a, cgen_stream_t stream)
   p.ci_total = off;
   p.n_cichunks = ch;
   p.n_tapgroups = ceil_div(p.taps, WG_MAXT);
-  {  // streaming kernel of round 5 (csrc/wgrad3.hip) where it serves the shape
-    Wg3Plan g3;
-    if (wg3_plan(a, g3)) {
-      CGEN_REQUIRE(g3.nsplit_total == a->nsplit, "cgen_conv2d_wgrad: nsplit %d != expected %d", a->nsplit, g3.nsplit_total);
-      wg3_launch_single(g3, (hipStream_t)stream);
-      return check_launch("cgen_conv2d_wgrad(stream)");
-    }
-  }
-  {  // tiled bf16 kernel when the shape allows it
-    int segc[CGEN_MAX_SEG];
-    for (int s = 0; s < a->nseg; ++s) segc[s] = a->seg[s].c;
-    Wg2Geom g;
-    Wg2P q;
-    if (build_wg2(a, q, g)) {
-      CGEN_REQUIRE(g.nsplit == a->nsplit, "cgen_conv2d_wgrad: nsplit %d != expected %d", a->nsplit, g.nsplit);
-      q.dbg = env_int("CGEN_WG2_DBG", 0);
-      { const char* e = getenv("CGEN_WG2_STAMPS"); q.stamps = e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }
-      hipStream_t st = (hipStream_t)stream;
-      switch (g.ncf) {
-        case 1: launch_wgrad2_ks<1, 16>(q, g, st); break;
-        case 2: if (a->ks == 7 || g.njw == 16) launch_wgrad2_ks<2, 16>(q, g, st); else launch_wgrad2_ks<2, 12>(q, g, st); break;
-        case 4: launch_wgrad2_ks<4, 6>(q, g, st); break;
-        case 6: launch_wgrad2_ks<6, 4>(q, g, st); break;
-        default: launch_wgrad2_ks<8, 3>(q, g, st); break;
-      }
-      return check_launch("cgen_conv2d_wgrad(tile)");
-    }
-  }
-  // geometry must match what the caller sized the partial buffer with
-  int ns, pps;
-  wgrad_geometry(p.P, p.Co, (p.ci_total + 31) / 32, p.KS, ns, pps);
-  CGEN_REQUIRE(ns == a->nsplit, "cgen_conv2d_wgrad: nsplit %d != expected %d", a->nsplit, ns);
-  p.nsplit = ns; p.pix_per_split = pps;
+  wgrad_geometry(p.P, p.Co, (p.ci_total + 31) / 32, p.KS, p.nsplit, p.pix_per_split);
+  d.nsplit = p.nsplit;
+  d.ntc = wgrad_ntc(p.Co);
   p.gout = mk(a->gout);
   {
-    const int q = 4 * esz;
-    p.gout_vec = ((uintptr_t)a->gout.p % q == 0) && ((a->gout.sn * esz) % q == 0) && ((a->gout.sh * esz) % q == 0) && ((a->gout.sw * esz) % q == 0);
+    const int q = 4 * d.esz;
+    p.gout_vec = ((uintptr_t)a->gout.p % q == 0) && ((a->gout.sn * d.esz) % q == 0) && ((a->gout.sh * d.esz) % q == 0) && ((a->gout.sw * d.esz) % q == 0);
   }
   p.pw = a->partial_w; p.pb = a->partial_b;
-  return a->dtype == CGEN_F32 ? launch_wgrad<float>(p, (hipStream_t)stream) : launch_wgrad<h16_t>(p, (hipStream_t)stream);
+}
+
+extern "C" int cgen_conv2d_wgrad_plan(const cgen_wgrad_args* a, int32_t* tiled_out) {
+  if (!a || a->nseg < 1 || a->nseg > CGEN_MAX_SEG) return 0;
+  WgradDecision d;
+  wgrad_decide(a, d);
+  if (tiled_out) *tiled_out = d.kind;
+  return d.nsplit;
+}
+
+extern "C" int cgen_conv2d_wgrad_plan_record(const cgen_wgrad_args* a, int32_t* out) {
+  if (!a || a->nseg < 1 || a->nseg > CGEN_MAX_SEG) return 0;
+  WgradDecision d;
+  wgrad_decide(a, d);
+  if (out) {
+    for (int i = 0; i < CGEN_WGRAD_PLAN_INTS; ++i) out[i] = 0;
+    out[0] = d.kind; out[1] = d.nsplit;
+    if (d.kind == 0) {
+      const WgP& p = d.p;
+      int mask = 0;
+      for (int s = 0; s < p.nseg; ++s) mask |= (p.seg_vec[s] ? 1 : 0) << s;
+      out[2] = a->dtype; out[3] = d.ntc; out[4] = p.n_cichunks; out[5] = p.n_tapgroups; out[6] = p.pix_per_split;
+      out[7] = p.gout_vec; out[8] = mask; out[9] = p.pb ? 1 : 0;
+    } else if (d.kind == 1) {
+      const Wg2Geom& g = d.g2;
+      out[2] = g.ncf; out[3] = g.njw; out[4] = d.q2.KS; out[5] = g.cwin; out[6] = g.n_cwin; out[7] = g.n_co; out[8] = g.ntiles;
+      out[9] = g.tps; out[10] = g.dbuf; out[11] = (int32_t)g.lds; out[12] = d.q2.variant;
+    }
+  }
+  return d.nsplit;
+}
+
+extern "C" int cgen_conv2d_wgrad(const cgen_wgrad_args* a, cgen_stream_t stream) {
+  CGEN_REQUIRE(a && a->partial_w, "cgen_conv2d_wgrad: null args");
+  CGEN_REQUIRE(a->dtype == CGEN_F32 || a->dtype == CGEN_F16, "cgen_conv2d_wgrad: bad dtype");
+  CGEN_REQUIRE(a->nseg >= 1 && a->nseg <= CGEN_MAX_SEG && a->gout.p && a->gout.c > 0, "cgen_conv2d_wgrad: bad args");
+  WgradDecision d;
+  wgrad_decide(a, d);
+  // geometry must match what the caller sized the partial buffer with
+  CGEN_REQUIRE(d.nsplit == a->nsplit, "cgen_conv2d_wgrad: nsplit %d != expected %d", a->nsplit, d.nsplit);
+  hipStream_t st = (hipStream_t)stream;
+  if (d.kind >= 2) {
+    wg3_launch_single(d.g3, st);
+    return check_launch("cgen_conv2d_wgrad(stream)");
+  }
+  if (d.kind == 1) {
+    Wg2P& q = d.q2;
+    const Wg2Geom& g = d.g2;
+    { const char* e = getenv("CGEN_WG2_STAMPS"); q.stamps = e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }
+    switch (g.ncf) {
+      case 1: launch_wgrad2_ks<1, 16>(q, g, st); break;
+      case 2: if (a->ks == 7 || g.njw == 16) launch_wgrad2_ks<2, 16>(q, g, st); else launch_wgrad2_ks<2, 12>(q, g, st); break;
+      case 4: launch_wgrad2_ks<4, 6>(q, g, st); break;
+      case 6: launch_wgrad2_ks<6, 4>(q, g, st); break;
+      default: launch_wgrad2_ks<8, 3>(q, g, st); break;
+    }
+    return check_launch("cgen_conv2d_wgrad(tile)");
+  }
+  return a->dtype == CGEN_F32 ? launch_wgrad<float>(d.p, d.ntc, st) : launch_wgrad<h16_t>(d.p, d.ntc, st);
 }

@@ -237,6 +237,18 @@ typedef struct cgen_wgrad_args {
   float* partial_b;
 } cgen_wgrad_args;
 int cgen_conv2d_wgrad_plan(const cgen_wgrad_args* a, int32_t* tiled_out);
+/* The plan of the launch (additive in ABI 411: a new symbol).  Host code: no GPU needed, nothing is dereferenced.  Returns what
+ * cgen_conv2d_wgrad_plan returns (nsplit; 0: bad args, out[] untouched); when out != NULL, out[0 .. 23] is the record
+ * cgen_conv2d_wgrad launches from (entries not named are 0):  [0] kind (*tiled_out above)   [1] nsplit, and
+ *   kind 0, wgrad_kernel<T, NTC>:  [2] dtype (CGEN_F32 / CGEN_F16)   [3] NTC (1, 2, 4: 16 NTC output channels per workgroup)   [4] 32-wide
+ *     input-channel chunks, all segments   [5] tap groups of up to 9 taps   [6] pixels per split   [7] gout_vec (grad_out read four
+ *     elements at a time)   [8] bit s: segment s is read 16 bytes at a time   [9] 1: partial_b is written
+ *   kind 1, wgrad_tile_kernel<NCF, NJW, KS>:  [2] NCF   [3] NJW   [4] KS   [5] cwin (input channels per window)   [6] windows   [7] blocks
+ *     of 16 NCF output channels   [8] 8 x 16 pixel tiles   [9] tiles per split   [10] 1: two tile buffers   [11] LDS bytes
+ *     [12] variant, as wgrad_tile_mega_kernel switches on it
+ *   kinds 2, 3: nothing more. */
+#define CGEN_WGRAD_PLAN_INTS 24
+int cgen_conv2d_wgrad_plan_record(const cgen_wgrad_args* a, int32_t* out);
 /* Horizontally batched weight gradients.  The weight-gradient launches of a step are independent of each other; most of
  * them fill a fraction of the chip.  `plan` packs every problem the tiled 16-bit (CGEN_F16) kernel serves (eligible[i] = 1; the others
  * go through cgen_conv2d_wgrad) into a host blob: a table of problems followed by one {problem, split, window, co range}

@@ -73,6 +73,24 @@ def test_pure_queries_and_arg_validation_without_gpu():
     assert lib.conv2d_wgrad_plan(ctypes.byref(w), ctypes.byref(tiled)) >= 1 and tiled.value == 2
     w.dtype = 0  # f32: the generic kernel
     assert lib.conv2d_wgrad_plan(ctypes.byref(w), ctypes.byref(tiled)) >= 1 and tiled.value == 0
+    # cgen_conv2d_wgrad_plan_record is host code: what cgen_conv2d_wgrad_plan answers, and the record the launch is made from
+    rec = (ctypes.c_int32 * 24)(*([-1] * 24))
+    w.partial_b = None
+    assert lib.conv2d_wgrad_plan_record(ctypes.byref(w), rec) == lib.conv2d_wgrad_plan(ctypes.byref(w), None) == rec[1]
+    # wgrad_kernel<float, 2>: 32 channels = one chunk, 49 taps = six groups, vector loads on both sides, no bias partial
+    assert tuple(rec[:10]) == (0, rec[1], 0, 2, 1, 6, rec[6], 1, 1, 0) and rec[6] % 64 == 0 and not any(rec[10:])
+    w.partial_b = 4096
+    assert lib.conv2d_wgrad_plan_record(ctypes.byref(w), rec) == rec[1] and rec[9] == 1
+    w.dtype, w.ks = 1, 3  # 16-bit 3x3, 256 -> 256 on dense views: wgrad_tile_kernel<4, 6, 3>, windows of 32 channels, one tile buffer
+    w.n, w.h, w.w = 2, 6, 6
+    w.seg[0] = w.gout = _lib.View(4096, 6 * 6 * 256, 6 * 256, 256, 256, 0)
+    assert lib.conv2d_wgrad_plan_record(ctypes.byref(w), rec) == rec[1] == 1
+    assert tuple(rec[:13]) == (1, 1, 4, 6, 3, 32, 8, 4, 2, 2, 0, 45056, 9) and not any(rec[13:])
+    w.seg[0] = w.gout = _lib.View(4096, 6 * 6 * 128, 6 * 128, 128, 128, 0)  # 128 -> 128: the streaming kernel, nothing beyond kind and nsplit
+    assert lib.conv2d_wgrad_plan_record(ctypes.byref(w), rec) == rec[1] and rec[0] == 2 and not any(rec[2:])
+    w.nseg = 0
+    rec[0] = -7
+    assert lib.conv2d_wgrad_plan_record(ctypes.byref(w), rec) == 0 and rec[0] == -7  # (bad arguments: out[] untouched)
     # cgen_block3_plan is host code: what cgen_block3_supported answers, and the record the launch is made from
     blk = _lib.Block3Args()
     blk.dtype, blk.n, blk.h, blk.w, blk.nseg, blk.nout, blk.pre_act = _lib.F16, 2, 24, 24, 1, 1, 1
