@@ -317,6 +317,7 @@ PROTOTYPES = {
     "cgen_predictor_tiled_workspace": [C.POINTER(PredHead), i32, i32, C.POINTER(i64)],
     "cgen_predictor_tiled_fwd": [C.POINTER(PredHead), i32, i32, vp, vp, i64, vp, vp, vp, vp],
     "cgen_predictor_tiled_bwd": [C.POINTER(PredHead), i32, i32, vp, vp, i64, vp, vp, vp],
+    "cgen_predictor_tiled_plan": [C.POINTER(PredHead), i32, i32, C.POINTER(i32), i32, C.POINTER(i32)],
     "cgen_predictor_train_workspace": [C.POINTER(PredTrainHead), i32, i32, C.POINTER(i64)],
     "cgen_predictor_train_fwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, f32, vp, vp, vp, vp],
     "cgen_predictor_train_bwd": [C.POINTER(PredTrainHead), i32, i32, vp, vp, i64, vp, vp, vp],

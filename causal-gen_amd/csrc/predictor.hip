@@ -872,49 +872,77 @@ int tile_validate(const char* fn, const cgen_pred_head* heads, int nheads, int n
 
 #define TILE_LAUNCH(kern, blocks, ...) hipLaunchKernelGGL(kern, dim3((unsigned)(blocks)), dim3(TNT), 0, st, __VA_ARGS__)
 
+// ---- the plan of a launch: which instance, over how many workgroups.  One host function per launch; the launchers below and
+// cgen_predictor_tiled_plan both read it, so what the plan entry reports is what runs.
+enum { TILE_FWD = 0, TILE_BWD = 1, TILE_STEM_BWD = 2, TILE_TAIL = 3 };
+struct TilePlan {
+  int family, K, S, NP, CT, flag, L;  // flag: POOL of a forward conv, MODE of a data gradient, BWD of the tail
+  int64_t blocks;
+};
+
+// the 7x7 stem: 4 * CT == width, one channel group
+inline TilePlan tile_plan_stem(const PredGeo& g, int64_t pairs) {
+  const int nt = (g.h1 + 15) / 16;
+  return {TILE_FWD, 7, g.s1, 2, tile_ct(g.w), 0, 0, pairs * nt * nt};
+}
+
+// 3x3 layer L = 1..5
+inline TilePlan tile_plan_fwd(const PredGeo& g, int L, int64_t pairs) {
+  const TileLayer ly = tile_layer(g, L);
+  const int ct = tile_ct(ly.cout), np = ly.hout > 12 ? 2 : 1, nt = (ly.hout + 8 * np - 1) / (8 * np);
+  return {TILE_FWD, 3, ly.s, np, ct, L == 1 && g.pool ? 1 : 0, L, pairs * (ly.cout / (4 * ct)) * nt * nt};
+}
+
+inline TilePlan tile_plan_tail(int64_t pairs, bool bwd) { return {TILE_TAIL, 0, 0, 0, 0, bwd ? 1 : 0, 6, pairs}; }
+
+// data gradient of 3x3 layer L
+inline TilePlan tile_plan_bwd(const PredGeo& g, int L, int64_t pairs) {
+  const TileLayer ly = tile_layer(g, L);
+  const int ct = tile_ct(ly.cin), nb = (ly.hin + ly.s - 1) / ly.s, nt = (nb + 7) / 8;
+  return {TILE_BWD, 3, ly.s, 0, ct, L == 1 && g.pool ? 1 : 0, L, pairs * (ly.cin / (4 * ct)) * nt * nt};
+}
+
+inline TilePlan tile_plan_stem_bwd(const PredGeo& g, int64_t n) {
+  const int nb = (g.r + g.s1 - 1) / g.s1, nt = (nb + 15) / 16;
+  return {TILE_STEM_BWD, 7, g.s1, 0, 0, 0, 0, n * nt * nt};
+}
+
 // every layer of the forward, stem to tail, into the workspace
 template <bool BWD>
 int tile_forward(const char* fn, const TileArgs& p, hipStream_t st) {
   const PredGeo g = pred_geo(p.hd[0]);
   const int64_t pairs = (int64_t)p.n * p.nheads;
   {
-    const int ct = tile_ct(g.w), nt = (g.h1 + 15) / 16;
-    const int64_t blocks = pairs * nt * nt;  // 4 * CT == width: one channel group
-    TILE_CT_SWITCH(ct, if (g.s1 == 2) TILE_LAUNCH((ptile_conv_fwd<7, 2, 2, CT, false>), blocks, p, 0);
-                   else TILE_LAUNCH((ptile_conv_fwd<7, 1, 2, CT, false>), blocks, p, 0));
+    const TilePlan pl = tile_plan_stem(g, pairs);
+    TILE_CT_SWITCH(pl.CT, if (pl.S == 2) TILE_LAUNCH((ptile_conv_fwd<7, 2, 2, CT, false>), pl.blocks, p, 0);
+                   else TILE_LAUNCH((ptile_conv_fwd<7, 1, 2, CT, false>), pl.blocks, p, 0));
   }
   for (int L = 1; L <= 5; ++L) {
-    const TileLayer ly = tile_layer(g, L);
-    const int ct = tile_ct(ly.cout), np = ly.hout > 12 ? 2 : 1, nt = (ly.hout + 8 * np - 1) / (8 * np);
-    const int64_t blocks = pairs * (ly.cout / (4 * ct)) * nt * nt;
-    const bool pool = L == 1 && g.pool;
-#define TILE_FWD3(S, NP, POOL) TILE_LAUNCH((ptile_conv_fwd<3, S, NP, CT, POOL>), blocks, p, L)
-    TILE_CT_SWITCH(ct, if (ly.s == 1) { if (np == 2) TILE_FWD3(1, 2, false); else TILE_FWD3(1, 1, false); }
-                   else if (pool) { if (np == 2) TILE_FWD3(2, 2, true); else TILE_FWD3(2, 1, true); }
+    const TilePlan pl = tile_plan_fwd(g, L, pairs);
+    const int np = pl.NP;
+#define TILE_FWD3(S, NP, POOL) TILE_LAUNCH((ptile_conv_fwd<3, S, NP, CT, POOL>), pl.blocks, p, L)
+    TILE_CT_SWITCH(pl.CT, if (pl.S == 1) { if (np == 2) TILE_FWD3(1, 2, false); else TILE_FWD3(1, 1, false); }
+                   else if (pl.flag) { if (np == 2) TILE_FWD3(2, 2, true); else TILE_FWD3(2, 1, true); }
                    else { if (np == 2) TILE_FWD3(2, 2, false); else TILE_FWD3(2, 1, false); });
 #undef TILE_FWD3
   }
-  TILE_LAUNCH((ptile_tail<BWD>), pairs, p);
+  TILE_LAUNCH((ptile_tail<BWD>), tile_plan_tail(pairs, BWD).blocks, p);
   return check_launch(fn);
 }
 
 // data gradient of 3x3 layer L into the planes of layer L - 1 (the stem's, through the pool, for L == 1)
 void tile_bwd_layer(const TileArgs& p, const PredGeo& g, int L, hipStream_t st) {
-  const int64_t pairs = (int64_t)p.n * p.nheads;
-  const TileLayer ly = tile_layer(g, L);
-  const int ct = tile_ct(ly.cin), nb = (ly.hin + ly.s - 1) / ly.s, nt = (nb + 7) / 8;
-  const int64_t blocks = pairs * (ly.cin / (4 * ct)) * nt * nt;
-  const bool pool = L == 1 && g.pool;
-  TILE_CT_SWITCH(ct, if (ly.s == 1) TILE_LAUNCH((ptile_conv_bwd<1, CT, 0>), blocks, p, L);
-                 else if (pool) TILE_LAUNCH((ptile_conv_bwd<2, CT, 1>), blocks, p, L);
-                 else TILE_LAUNCH((ptile_conv_bwd<2, CT, 0>), blocks, p, L));
+  const TilePlan pl = tile_plan_bwd(g, L, (int64_t)p.n * p.nheads);
+  TILE_CT_SWITCH(pl.CT, if (pl.S == 1) TILE_LAUNCH((ptile_conv_bwd<1, CT, 0>), pl.blocks, p, L);
+                 else if (pl.flag) TILE_LAUNCH((ptile_conv_bwd<2, CT, 1>), pl.blocks, p, L);
+                 else TILE_LAUNCH((ptile_conv_bwd<2, CT, 0>), pl.blocks, p, L));
 }
 
 // dx from the stem's planes
 void tile_bwd_stem(const TileArgs& p, const PredGeo& g, hipStream_t st) {
-  const int nb = (g.r + g.s1 - 1) / g.s1, nt = (nb + 15) / 16;
-  if (g.s1 == 2) TILE_LAUNCH((ptile_stem_bwd<2>), (int64_t)p.n * nt * nt, p);
-  else TILE_LAUNCH((ptile_stem_bwd<1>), (int64_t)p.n * nt * nt, p);
+  const TilePlan pl = tile_plan_stem_bwd(g, p.n);
+  if (pl.S == 2) TILE_LAUNCH((ptile_stem_bwd<2>), pl.blocks, p);
+  else TILE_LAUNCH((ptile_stem_bwd<1>), pl.blocks, p);
 }
 
 int tile_backward(const char* fn, const TileArgs& p, hipStream_t st) {
@@ -986,6 +1014,30 @@ extern "C" int cgen_predictor_tiled_workspace(const cgen_pred_head* heads, int32
   CGEN_REQUIRE(n >= 1, "cgen_predictor_tiled_workspace: bad batch %d", n);
   CGEN_REQUIRE(tile_shapes_ok(heads, nheads), "cgen_predictor_tiled_workspace: the tiled path does not take these heads");
   *floats = tile_ws(heads, nheads, n);
+  return CGEN_OK;
+}
+
+extern "C" int cgen_predictor_tiled_plan(const cgen_pred_head* heads, int32_t nheads, int32_t n, int32_t* records, int32_t max,
+                                         int32_t* count) {
+  CGEN_REQUIRE(count, "cgen_predictor_tiled_plan: null count");
+  CGEN_REQUIRE(n >= 1 && (int64_t)n * CGEN_PRED_MAX_HEADS * 4096 < INT32_MAX, "cgen_predictor_tiled_plan: bad batch %d", n);
+  CGEN_REQUIRE(tile_shapes_ok(heads, nheads), "cgen_predictor_tiled_plan: the tiled path does not take these heads");
+  CGEN_REQUIRE(!records || max >= 0, "cgen_predictor_tiled_plan: negative record capacity");
+  const PredGeo g = pred_geo(heads[0]);
+  const int64_t pairs = (int64_t)n * nheads;
+  TilePlan pl[CGEN_PRED_PLAN_LAUNCHES];
+  int k = 0;
+  pl[k++] = tile_plan_stem(g, pairs);
+  for (int L = 1; L <= 5; ++L) pl[k++] = tile_plan_fwd(g, L, pairs);
+  pl[k++] = tile_plan_tail(pairs, false);
+  for (int L = 5; L >= 1; --L) pl[k++] = tile_plan_bwd(g, L, pairs);
+  pl[k++] = tile_plan_stem_bwd(g, n);
+  *count = k;
+  for (int i = 0; records && i < k && i < max; ++i) {
+    int32_t* r = records + (int64_t)i * CGEN_PRED_PLAN_FIELDS;
+    r[0] = pl[i].family; r[1] = pl[i].K; r[2] = pl[i].S; r[3] = pl[i].NP; r[4] = pl[i].CT; r[5] = pl[i].flag; r[6] = pl[i].L;
+    r[7] = (int32_t)pl[i].blocks;
+  }
   return CGEN_OK;
 }
 

@@ -738,6 +738,19 @@ int cgen_predictor_tiled_fwd(const cgen_pred_head* heads, int32_t nheads, int32_
                              float* terms, float* outs, float* loss, cgen_stream_t);
 int cgen_predictor_tiled_bwd(const cgen_pred_head* heads, int32_t nheads, int32_t n, const float* x, float* ws, int64_t ws_floats,
                              const float* coef_dev, float* dx, cgen_stream_t);
+/* The plan of the tiled placement's launches (additive in ABI 411: a new symbol).  Host code: no GPU needed, no pointer of a
+ * record is dereferenced.  *count = CGEN_PRED_PLAN_LAUNCHES; when records != NULL, the first min(max, *count) records of
+ * CGEN_PRED_PLAN_FIELDS int32 each are written, in launch order: the forward call's 7 launches (stem, 3x3 layers 1..5, tail), then
+ * the 6 data-gradient launches the backward call adds after the same forward (layers 5..1, then the stem's into dx).  A record is
+ *   [0] family: 0 ptile_conv_fwd<K, S, NP, CT, POOL>, 1 ptile_conv_bwd<S, CT, MODE>, 2 ptile_stem_bwd<S>, 3 ptile_tail
+ *   [1] K  [2] S  [3] NP  [4] CT  (0 where the kernel has no such parameter)
+ *   [5] POOL (family 0), MODE (family 1), 0 otherwise (the tail is reported as the forward call runs it)
+ *   [6] layer: 0 the stem, 1..5 the 3x3 layers, 6 the tail
+ *   [7] workgroups of the launch
+ * The launchers read the same host functions, so the record is what runs.  Shapes as cgen_predictor_tiled_supported. */
+#define CGEN_PRED_PLAN_LAUNCHES 13
+#define CGEN_PRED_PLAN_FIELDS 8
+int cgen_predictor_tiled_plan(const cgen_pred_head* heads, int32_t nheads, int32_t n, int32_t* records, int32_t max, int32_t* count);
 
 /* ------------------------------------------------------------------ anticausal predictors, TRAINING mode (additive in ABI 411)
  * The same CNN with batch-statistic BatchNorm (pgm/layers.py CNN in train mode; train_pgm.py sup_epoch, --setup sup_aux): the

@@ -114,6 +114,22 @@ def test_pure_queries_and_arg_validation_without_gpu():
     assert tuple(rec[:5]) == (1, 2, 8, 18, 18) and tuple(rec[6:10]) == (0, 3, 3, 4) and not any(rec[10:])
     b4.b = 56
     assert lib.block4_plan(ctypes.byref(b4), rec) == 0 and lib.block4_plan(ctypes.byref(b4), None) == 0 and rec[0] == 1  # (declined: out[] untouched)
+    # cgen_predictor_tiled_plan is host code: the 13 launches of the tiled placement, read from the functions the launchers read.
+    # ukbb192 (1 x 192 x 192, width 16, 4 heads, B = 32): stride-2 stem, the pool inside layer 1, 16-pixel tiles down to 24 x 24
+    hd = (_lib.PredHead * 4)()
+    for h in hd:
+        h.c, h.res, h.width, h.nout, h.kind, h.obs_stride = 1, 192, 16, 2, _lib.PRED_NORMAL, 1
+    prec = (ctypes.c_int32 * (8 * 13))(*([-1] * 104))
+    cnt = ctypes.c_int32(0)
+    lib.predictor_tiled_plan(hd, 4, 32, prec, 13, ctypes.byref(cnt))
+    assert cnt.value == 13
+    got = [tuple(prec[8 * i:8 * i + 8]) for i in range(13)]
+    assert got[0] == (0, 7, 2, 2, 4, 0, 0, 128 * 36) and got[1] == (0, 3, 2, 2, 8, 1, 1, 128 * 4)  # ptile_conv_fwd<7,2,2,4,false>, <3,2,2,8,true>
+    assert got[6] == (3, 0, 0, 0, 0, 0, 6, 128) and got[7] == (1, 3, 2, 0, 8, 0, 5, 128 * 2 * 1)   # ptile_tail, ptile_conv_bwd<2,8,0>
+    assert got[11] == (1, 3, 2, 0, 4, 1, 1, 128 * 9) and got[12] == (2, 7, 2, 0, 0, 0, 0, 32 * 36)  # ptile_conv_bwd<2,4,1>, ptile_stem_bwd<2>
+    hd[1].width = 8  # unequal widths: refused, the records untouched
+    prec[0] = -7
+    assert lib._raw_cgen_predictor_tiled_plan(hd, 4, 32, prec, 13, ctypes.byref(cnt)) != 0 and prec[0] == -7
     # argument validation happens before any launch, so it is testable on a CPU-only host
     a = _lib.ConvArgs()
     a.dtype = 7
