@@ -207,6 +207,7 @@ METRIC_NONE, METRIC_SIGMOID, METRIC_SOFTMAX, METRIC_TANH = 0, 1, 2, 3
 METRIC_N, METRIC_CORRECT, METRIC_ABS_ERR, METRIC_SKIPPED, METRIC_OVERFLOW = 0, 1, 2, 3, 4
 METRIC_MAX_VARS, METRIC_ACC = 8, 8
 STREAM_AUGMENT = 980  # Philox stream id of cgen_batch_augment (the list of taken ids is in csrc/common.h)
+STREAM_GUMBEL, STREAM_GUMBEL_COUNT = 989, 8  # 989 + k: the k-th Gumbel-max mechanism's uniforms (PgmCounterfactual.run(rng=)); 989 .. 996
 PRED_NORMAL, PRED_CATEGORICAL, PRED_BERNOULLI = 0, 1, 2
 PRED_MAX_HEADS, PRED_MAX_OUT = 4, 16
 MLP_MAX_IN, MLP_MAX_WIDTH = 8, 64
@@ -340,6 +341,7 @@ PROTOTYPES = {
     "cgen_rocauc": [vp, vp, vp, i64, i32, i64, vp, vp, vp],
     "cgen_image_dist": [i32, i64, vp, vp, vp, vp, vp, vp],
     "cgen_philox_normal": [vp, i64, vp, u32, vp],
+    "cgen_philox_uniform": [vp, i64, vp, u32, vp],
     "cgen_rng_advance": [vp, u64, vp],
 }
 _RESTYPES = {"cgen_last_error": C.c_char_p, "cgen_conv2d_last_kernel": C.c_char_p}

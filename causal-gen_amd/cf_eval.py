@@ -50,8 +50,9 @@ def metric_specs(dataset: str, min_max: Optional[Dict[str, Sequence[float]]] = N
     ukbb: ``sex`` and ``mri_seq`` ROC-AUC and accuracy; ``age``, ``brain_volume`` and ``ventricle_volume`` mean absolute error in
     original units (both sides taken from the [-1, 1] normalisation back to [min, max]; volumes in ml, i.e. / 1000).
     morphomnist: digit accuracy; thickness and intensity MAE, both sides unnormalised with ``min_max[k] = (min, max)`` (the data
-    set's; without it the error stays on the [-1, 1] scale).  cmnist: digit and colour accuracy.  mimic (the table only -- there is
-    no mimic predictor here; for predictions a reference predictor already produced, so every transform is "none"): sex and finding
+    set's; without it the error stays on the [-1, 1] scale).  cmnist: digit and colour accuracy.  mimic (the table for predictions that are
+    probabilities already -- ``ChestPredictor.predict()``'s or a reference predictor's -- so every transform is "none";
+    ``chest_metric_specs()`` is the table for ``predictor_resnet.ChestPredictor``'s raw head outputs): sex and finding
     ROC-AUC and accuracy, age MAE with (v + 1) * 50 on both sides, race accuracy and one-vs-rest macro ROC-AUC.
     ``raw=True``: the predictions are raw head outputs (``predictor.raw_outputs``); ``raw=False``: they are ``predict()``'s."""
     ds = dataset or ""

@@ -1,7 +1,8 @@
 """Counterfactual fine-tuning on the GPU -- the ``is_train`` branch of ``cf_epoch`` (``src/pgm/train_cf.py:140-180``) as a fixed launch
 sequence without a host read:
 
-    [step_from: counterfactual parents (cgen_pgm_counterfactual)] -> rng advance -> factual ELBO, abduction and counterfactual replay
+    [step_from: the Gumbel-max uniforms of the PGM, if it has such a mechanism (cgen_philox_uniform on the engine's Philox state) ->
+    counterfactual parents (cgen_pgm_counterfactual)] -> rng advance -> factual ELBO, abduction and counterfactual replay
     on one tape (HVAE._run_dscm_forward; step_from: the augment launch is its first) -> anticausal predictor forward on cf_x ->
     non-finite counts of the head outputs x2 -> the Lagrangian (cgen_cf_lagrange) -> predictor input gradient at 1 / B ->
     d cf_x / d head outputs -> ELBO seeds -> engine backward -> global grad-norm with the multiplier's slot -> clip / skip ->
@@ -14,6 +15,11 @@ train_cf.py:205-210 is a block of running sums on the device, read once per epoc
 
 f32 engine, one particle, one GPU; ``DSCM.forward`` and its autograd path are untouched and remain the host composition this replaces.
 
+The predictor sits behind one seam (``cf_heads``): its variables, its records for a static batch, a forward that writes per-sample
+terms and their sum, a backward that writes ``d aux / d cf_x`` at the device coefficient 1 / B.  ``CnnHeads`` serves the predictors of
+``predictor.make_predictor`` (morphomnist, cmnist, ukbb: the launches the step always had), ``ChestHeads`` mimic's
+``predictor_resnet.ChestPredictor`` (one trunk, four heads, ``terms`` [B, 4], the observations read in place at their strides).
+
 Device buffers (all f32 unless said):
   ``lag``  [4] = {lmbda, exp_avg, exp_avg_sq, EMA of lmbda}; ``dscm.lmbda.data`` is ``lag[0:1]``, ``ema_model.lmbda.data`` is ``lag[3:4]``
   ``res``  [4] = {loss, aux_loss, d loss / d lmbda, w = d loss / d elbo}          (cgen_cf_lagrange)
@@ -25,12 +31,12 @@ Device buffers (all f32 unless said):
 """
 import copy
 import ctypes as C
-import math
 import random
 
 import torch
 
 from . import _lib
+from .cf_heads import heads_for, kind_of
 from .engine import StaticParents, compact_parents
 from .step_tail import (STATE_FLOATS, HyperParams, StepTail, capture, check_index, mark_weights_written, normalize_columns, pin_drop_cond,
                         ranges_where)
@@ -56,8 +62,9 @@ def _check(dscm, args, lr, lr_lagrange, process_group):
                          f"{type(vae).__name__} with {type(lk).__name__} has none")
     if not (float(lr) > 0.0 and float(lr_lagrange) > 0.0):
         raise ValueError(f"CfTrainStep: learning rates must be positive (lr = {lr}, lr_lagrange = {lr_lagrange})")
-    if dscm.predictor is None or not hasattr(dscm.predictor, "_heads"):
-        raise ValueError("CfTrainStep: the predictor must come from predictor.make_predictor (ChestPredictor is not served)")
+    if dscm.predictor is None or kind_of(dscm.predictor) is None:
+        raise ValueError("CfTrainStep: the predictor must be one of predictor.make_predictor's (CNN heads) or a "
+                         f"predictor_resnet.ChestPredictor; {type(dscm.predictor).__name__} is neither")
 
 
 class CfTrainStep:
@@ -75,6 +82,7 @@ class CfTrainStep:
         self.vae, self.pred = dscm.vae.to(dev), dscm.predictor.to(dev)
         self.eng = eng = self.vae.engine()
         dev = self.device = eng.device
+        self.heads = heads_for(self.pred, dev)
         n = eng.flat_p.numel()
         self.tail = StepTail(self.lib, n, dev, self.NORM_BLOCKS, extra_norm_slots=1)
         self.state = self.tail.state
@@ -112,41 +120,17 @@ class CfTrainStep:
         return HyperParams(self.lr, (float(a.betas[0]), float(a.betas[1])), 1e-8, float(a.wd), float(a.grad_clip), float(a.grad_skip), 1,
                            float(a.ema_rate), self.EMA_UPDATE_AFTER, True)
 
-    def _pred_records(self, B, xshape, at, dense):
-        """The predictor's head records for a static batch: ``at(var)`` = (address, row stride in floats) of a scored variable's
-        rows, ``dense[var]`` the contiguous [B, k] buffer of a context variable (predictor._records on caller-owned buffers)."""
-        from .predictor import fill_head
-
-        heads = self.pred._heads()
-        recs = (_lib.PredHead * len(heads))()
-        keep = []
-        for r, hd in zip(recs, heads):
-            y = dense[hd.ctx_var] if hd.cnn.context_dim else None
-            fill_head(r, hd, xshape, self.pred.std_fixed, None if y is None else y.shape[1])
-            wb = hd.cnn.folded(self.device)
-            keep.append(wb)
-            for i, (w, b) in enumerate(wb):
-                r.w[i], r.b[i] = w.data_ptr(), b.data_ptr()
-            if y is not None:
-                r.y = y.data_ptr()
-            r.obs, r.obs_stride = at(hd.var)
-        return recs, keep
-
     def _pred_vars(self):
         """(variables the image heads score, their context variables, every variable the predictor reads), in first-use order"""
-        heads = self.pred._heads()
-        scored = [hd.var for hd in heads]
-        ctx = list(dict.fromkeys(hd.ctx_var for hd in heads if hd.ctx_var is not None))
-        extra = [v for sh in self.pred._scalar_heads() for v in (sh.var, *sh.inputs)]
-        return scored, ctx, list(dict.fromkeys(scored + ctx + extra))
+        h = self.heads
+        return h.scored, h.ctx, h.every
 
     def _finish_entry(self, ent, xshape, at, dense, obs_views):
-        from . import predictor as P
-
+        """The predictor's records for a static batch (``at(var)`` = (address, row stride in floats) of a variable's rows,
+        ``dense[var]`` the contiguous [B, k] buffer of a context variable) and the buffers its launches write."""
         B = int(xshape[0])
-        recs, keep = self._pred_records(B, xshape, at, dense)
-        ent.update(B=B, xshape=tuple(xshape), recs=recs, keep=keep, route=P._route(self.pred, recs, B, self.device),
-                   terms=torch.zeros(B, len(recs), device=self.device), loss=torch.zeros(1, device=self.device),
+        ent.update(B=B, xshape=tuple(xshape), plan=self.heads.build(B, xshape, at, dense),
+                   terms=torch.zeros(B, self.heads.n_terms, device=self.device), loss=torch.zeros(1, device=self.device),
                    inv_b=torch.full((1,), 1.0 / B, device=self.device), obs_views=obs_views, graph=None, out3=None)
         return ent
 
@@ -235,14 +219,13 @@ class CfTrainStep:
         """step_from, inside the step: one launch for the counterfactual table and both compact parents, then the dense copies of
         the predictor's context columns"""
         ds, cfm = ent["ds"], ent["cfm"]
-        _, ent["pa"], ent["cf_pa"] = cfm.run(ds.pa, ent["x"].index_buf, ds.pa, ent["do_index"], do_mask_dev=ent["mask"])
+        self.eng.rng_ptr()  # (creates the Philox state on first use; the launch below reads it, the step's advance follows)
+        _, ent["pa"], ent["cf_pa"] = cfm.run(ds.pa, ent["x"].index_buf, ds.pa, ent["do_index"], do_mask_dev=ent["mask"], rng=self.eng.rng)
         for dst, src in ent["gather"]:
             dst.copy_(src)
 
     def _fwd_bwd(self, ent):
         """Forward, the Lagrangian and the backward pass of one static batch.  Returns the device tensor [elbo, nll, kl]."""
-        from . import predictor as P
-
         m, eng, lib = self.vae, self.eng, self.lib
         B = ent["B"]
         m.__dict__["_beta_dev"] = self.coef.data_ptr() + 8
@@ -251,8 +234,8 @@ class CfTrainStep:
         finally:
             m.__dict__["_beta_dev"] = None
         st = eng.stream
-        P._fwd(lib, ent["route"], ent["recs"], B, cf_x, ent["terms"], None, ent["loss"])
-        host = ent["host"] = self._scalar_nll(ent["obs_views"], B)  # heads that see no image (UKBB's age): a device scalar, no gradient
+        self.heads.forward(ent["plan"], cf_x, ent["terms"], ent["loss"])
+        host = ent["host"] = self.heads.scalar_nll(ent["obs_views"], B)  # heads that see no image (UKBB's age): a device scalar, no gradient
         (rec_params, cf_params), = m.__dict__["_saved_cf"][0]
         nb = self.NONFINITE_BLOCKS
         for i, t in enumerate((rec_params, cf_params)):
@@ -269,7 +252,7 @@ class CfTrainStep:
         lib.cf_lagrange(C.byref(q), st)
         # d aux_loss / d cf_x, then through cf_x = clamp(cf_loc + cf_scale (x - rec_loc) / rec_scale) into the head gradients
         dx = torch.empty_like(cf_x)
-        P._bwd(lib, ent["route"], ent["recs"], B, cf_x, ent["inv_b"], dx)
+        self.heads.backward(ent["plan"], cf_x, ent["inv_b"], dx)
         g_rec, g_cfp = eng.seed_grad(rec_params), eng.seed_grad(cf_params)
         if m.likelihood.kind == "dgauss":
             eng.lib.cf_dgauss_bwd(eng.dt, B, R, R, Cx, rec_params.cv(), cf_params.cv(), xin.cv(), dx.data_ptr(), S, g_rec.cv(), g_cfp.cv(), st)
@@ -277,7 +260,7 @@ class CfTrainStep:
             eng.lib.cf_dmol_bwd(eng.dt, B, R, R, m._dmol_mode(True), rec_params.cv(), cf_params.cv(), xin.cv(), dx.data_ptr(), S, g_rec.cv(),
                                 g_cfp.cv(), st)
         eng.launches += 1
-        ent["dx"] = dx
+        ent["dx"], ent["cf_x"] = dx, cf_x
         # the factual ELBO's seeds, read by the kernels from `coef` (what cgen_cf_lagrange just wrote)
         eng.kl_coef_ptr = self.coef.data_ptr() + 4
         eng.like_coef_ptr = self.coef.data_ptr()
@@ -290,23 +273,6 @@ class CfTrainStep:
             eng.launches += 1
         eng.backward()
         return out3
-
-    @torch.no_grad()
-    def _scalar_nll(self, views, B):
-        """``predictor._host_nll`` of the heads that see no image, as plain tensor ops on the static columns: ``Normal.log_prob``'s
-        own expression without ``torch.distributions`` (whose argument validation reads the device, which a capture refuses).
-        None when the predictor has no such head."""
-        total = None
-        for sh in self.pred._scalar_heads():
-            ctx = torch.cat([views[v].reshape(B, -1) for v in sh.inputs], dim=-1)
-            loc, logscale = sh.mlp(ctx).chunk(2, dim=-1)
-            if sh.tanh_loc:
-                loc = torch.tanh(loc)
-            scale = self.pred.f(logscale)
-            y = views[sh.var].reshape(loc.shape)
-            nll = (((y - loc) ** 2) / (2 * scale ** 2) + scale.log() + math.log(math.sqrt(2 * math.pi))).sum()
-            total = nll if total is None else total + nll
-        return None if total is None else total.reshape(1)
 
     def _lagrange_step(self, stream):
         a = self.args
@@ -340,6 +306,7 @@ class CfTrainStep:
         self.it += 1
         if ent["graph"] is not None:
             ent["graph"].replay()
+            self.heads.replayed(ent["plan"])
         else:
             ent["out3"] = eager = self._body(ent)
             if self.use_graph:
@@ -369,7 +336,10 @@ class CfTrainStep:
         variable (``columns=`` at construction, default: side by side in ``pgm.variables`` order).  The intervention takes the
         value of `do_var` (default ``args.do_pa``, else a random variable of the PGM) from rows `do_index` of the same table
         (default ``index[randperm(B)]``, train_cf.py:149).  The index, the permutation and the intervention's mask word are
-        copied into static buffers: another `do_var` is another mask word for the same graph."""
+        copied into static buffers: another `do_var` is another mask word for the same graph.  A Gumbel-max mechanism (ChestPGM's
+        ``finding | age``) takes its uniforms from the engine's Philox state (``PgmCounterfactual.run(rng=)``), read before the
+        step's advance on stream ids nothing else uses, so they are this step's alone and resume with ``state_dict()``.  (With an
+        injected ``vae.noise`` the engine does not advance and the uniforms repeat from step to step: tests only.)"""
         ent = self._static_from(ds, index, train)
         B = ent["B"]
         if do_index is None:

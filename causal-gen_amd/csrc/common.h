@@ -228,7 +228,10 @@ __device__ __forceinline__ float block_sum_256(float v, float* sm) {
 //   979              the config-1 model's samplers (simple_vae.py)
 //   980              cgen_batch_augment's crop / flip draws (keyed by data set row)
 //   981 .. 988       Dropout of the eight residual blocks of cgen_resnet_train_fwd (csrc/predictor_resnet_train.inc)
+//   989 .. 996       Gumbel-max uniforms of cgen_pgm_counterfactual, drawn by cgen_philox_uniform: 989 + k for the k-th Gumbel-max
+//                    mechanism of a PGM (CGEN_PGM_MAX_MECH = 8 mechanisms at most)
 #define CGEN_STREAM_AUGMENT 980u
+#define CGEN_STREAM_GUMBEL 989u
 struct Philox {
   static __device__ __forceinline__ void round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
     const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;

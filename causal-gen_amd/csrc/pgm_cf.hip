@@ -11,7 +11,7 @@
 // each layer's weights staged in LDS once and applied to both contexts side by side; the hidden pre-activations ping-pong between
 // two [width][row] arrays per context.  After the walk wave w writes columns w, w + 8, ... of its rows of `cf` (the do row's bits
 // for a masked mechanism, Val for an MLP mechanism, the observation's bits for everything else) and wave 0 the two parents rows.
-// No atomics, no workspace, no RNG (the caller draws the Gumbel-max uniforms); every store is plain C++; reruns are bit-identical.
+// No atomics, no workspace, no RNG (the caller supplies the Gumbel-max uniforms, with cgen_philox_uniform or its own draws); every store is plain C++; reruns are bit-identical.
 // Precision follows pgm.hip: buffers and activations f32; dot products, the spline inverse, the affine round trip (eps stays in its
 // f64 register between abduction and prediction), the Gumbel algebra and the log-standardisation in f64, rounded to f32 once.
 #include "pgm_common.h"

@@ -126,7 +126,7 @@ class PgmCounterfactual:
 
     # -- public -------------------------------------------------------------------------------------------
     def run(self, table: Tensor, index: Optional[Tensor] = None, do_table: Optional[Tensor] = None, do_index: Optional[Tensor] = None,
-            do_vars: Optional[Sequence[str]] = None, do_mask_dev: Optional[Tensor] = None, uniforms=None, generator=None):
+            do_vars: Optional[Sequence[str]] = None, do_mask_dev: Optional[Tensor] = None, uniforms=None, generator=None, rng: Optional[Tensor] = None):
         """Counterfactuals of rows ``index`` of ``table`` (all rows, in order, without an index) under ``do`` of the variables
         ``do_vars`` -- or of those whose bit (position in ``pgm.mechanisms()``) is set in the one-element int32 device tensor
         ``do_mask_dev``, read when the launch runs -- with the values of rows ``do_index`` of ``do_table``.
@@ -136,7 +136,11 @@ class PgmCounterfactual:
         the next call with as many rows; ``noise(B)`` is the abducted noise of that call.  Only enqueues: inside
         ``torch.cuda.graph`` the tensors passed in are the graph's inputs, their CONTENTS may change between replays.
         ``uniforms``: ``[B, classes]`` f32 per Gumbel-max variable ({variable: tensor}, or the tensor when there is one such
-        variable); drawn with ``torch.rand`` on the device when absent."""
+        variable).  Without them, ``rng`` -- the device ``{seed, offset}`` tensor of an engine (``eng.rng`` after ``eng.rng_ptr()``)
+        -- fills each such variable's static buffer with one ``cgen_philox_uniform`` launch on the current stream (stream id
+        ``989 + k`` for the k-th Gumbel-max mechanism): the state is read when the launch runs and is not advanced, so a replay
+        draws at the state's current offset and torch's generators are not touched.  With neither, the uniforms are drawn with
+        ``uniform_`` on the device (``generator``), as before.  ``uniforms`` for a variable together with ``rng`` raises."""
         table = self._table(table, "the table")
         index, do_index = self._index(index, "the index"), self._index(do_index, "do_index")
         B = int(index.numel()) if index is not None else int(table.shape[0])
@@ -164,10 +168,19 @@ class PgmCounterfactual:
                 if len(self.gumbel) != 1:
                     raise ValueError("PgmCounterfactual.run: name the Gumbel-max variables of `uniforms` ({variable: tensor})")
                 uniforms = {self.vars[self.gumbel[0]]: uniforms}
-            for i in self.gumbel:
+            if rng is not None:
+                if rng.dtype != torch.int64 or rng.numel() != 2 or rng.device.type != "cuda" or not rng.is_contiguous():
+                    raise ValueError("PgmCounterfactual.run: rng must be the device {seed, offset} int64 tensor of an engine")
+                given = [self.vars[i] for i in self.gumbel if uniforms is not None and uniforms.get(self.vars[i]) is not None]
+                if given:
+                    raise ValueError(f"PgmCounterfactual.run: give uniforms or rng, not both (uniforms were given for {given})")
+            for k, i in enumerate(self.gumbel):
                 buf = ent["uniforms"][i]
                 u = None if uniforms is None else uniforms.get(self.vars[i])
-                if u is None:
+                if u is None and rng is not None:
+                    self.lib.philox_uniform(buf.data_ptr(), buf.numel(), rng.data_ptr(), _lib.STREAM_GUMBEL + k,
+                                            torch.cuda.current_stream(self.device).cuda_stream)
+                elif u is None:
                     buf.uniform_(generator=generator)
                 else:
                     if tuple(u.shape) != tuple(buf.shape):

@@ -232,20 +232,53 @@ class ChestPredictor(_AnticausalPredictor):
             raise ValueError(f"ChestPredictor: built for square images of input_res {self.input_res} within {MIN_RES}..{MAX_RES}, "
                              f"got {tuple(x.shape[-2:])}")
 
-    def _run(self, x: Tensor, obs, need_obs: bool):
-        """Everything a launch plan needs: the argument record, the tensors it points into, the workspace."""
-        self._check(x)
-        lib = _lib.require_gpu()
-        dev, B, R = x.device, x.shape[0], x.shape[-1]
+    def _net_args(self, dev, R):
+        """(the argument record with the network's side filled in -- weight images, GroupNorm parameters, heads --, what it points into)"""
         im = self._images(dev)
         a = _lib.ResnetArgs()
         a.res, a.std_fixed = R, self.std_fixed
-        keep = [im]
         for i in range(_lib.RESNET_CONVS):
             a.img_fwd[i], a.img_dg[i] = im["fwd"][i].data_ptr(), im["dg"][i].data_ptr()
             a.gamma[i], a.beta[i] = im["gamma"][i].data_ptr(), im["beta"][i].data_ptr()
         for h in range(4):
             a.fc_w[h], a.fc_b[h] = im["fc_w"][h].data_ptr(), im["fc_b"][h].data_ptr()
+        return a, im
+
+    def _plan(self, n: int, dev, at):
+        """``_run``'s record on caller-owned buffers: ``at(var)`` = (device address, row stride in floats) of a variable's rows --
+        a static buffer, or a column of a wider table (``race``: three adjacent columns from that address; ``finding`` is both the
+        scored variable and ``encoder_a``'s context, read in place at its stride).  Nothing is copied, so a captured launch sees
+        whatever the buffers hold when it replays.  The image is not part of the record: ``_fwd(run, ..., x=...)`` binds it at
+        launch time and ``_bwd`` reads the workspace.  The record holds its workspace: a later, larger call may give the
+        predictor another one, this one stays allocated for as long as the record (and a graph captured over it) lives."""
+        lib = _lib.require_gpu()
+        dev = torch.device(dev)
+        if dev.index is None:  # (the cached weight images and workspace are keyed by the device as tensors name it)
+            dev = torch.device(dev.type, torch.cuda.current_device())
+        n, R = int(n), self.input_res
+        if n < 1 or self.input_channels != 1 or not MIN_RES <= R <= MAX_RES:
+            raise ValueError(f"ChestPredictor: needs B >= 1, input_channels 1 and input_res within {MIN_RES}..{MAX_RES}, got B = {n}, "
+                             f"input_channels {self.input_channels}, input_res {R}")
+        a, im = self._net_args(dev, R)
+        for h, var in enumerate(_VARS):
+            ptr, stride = at(var)
+            if not ptr or int(stride) < (3 if var == "race" else 1):
+                raise ValueError(f"ChestPredictor: {var!r} at address {ptr} with a row stride of {stride} floats")
+            a.obs[h], a.obs_stride[h] = int(ptr), int(stride)
+            if var == "finding":
+                a.ctx, a.ctx_stride = int(ptr), int(stride)
+        need = _lib.i64(0)
+        lib.resnet_workspace(n, R, ctypes.byref(need))
+        ws = _cached(self, "_ws", need.value, dev)
+        return {"lib": lib, "args": a, "keep": [im], "ws": ws, "n": n, "res": R, "x": None, "token": object()}
+
+    def _run(self, x: Tensor, obs, need_obs: bool):
+        """Everything a launch plan needs: the argument record, the tensors it points into, the workspace."""
+        self._check(x)
+        lib = _lib.require_gpu()
+        dev, B, R = x.device, x.shape[0], x.shape[-1]
+        a, im = self._net_args(dev, R)
+        keep = [im]
         if "finding" not in obs:
             raise ValueError("ChestPredictor: the age head needs obs['finding']")
         fnd = _col(obs["finding"], B, dev)
@@ -263,11 +296,25 @@ class ChestPredictor(_AnticausalPredictor):
         ws = _cached(self, "_ws", need.value, dev)
         return {"lib": lib, "args": a, "keep": keep, "ws": ws, "n": B, "res": R, "x": x, "token": object()}
 
-    def _fwd(self, run, terms, outs, loss):
-        t, o, l = (v.data_ptr() if v is not None else None for v in (terms, outs, loss))
-        ws, x = run["ws"], run["x"]
+    def _ran(self, run):
+        """Host-side note that `run`'s forward is the last one enqueued: ``_fwd`` leaves it, and so does whoever replays a graph
+        captured over ``_fwd`` (a replay runs no Python).  ``_ChestNLL.backward`` reads the token (its forward's state may be gone),
+        ``trunk_activations`` the shape and the record's workspace, whatever ``_ws`` is by now."""
         self.__dict__["_ws_token"] = run["token"]
         self.__dict__["_ws_shape"] = (run["n"], run["res"])
+        self.__dict__["_ws_last"] = run["ws"]
+
+    def _fwd(self, run, terms, outs, loss, x: Tensor = None):
+        """The forward launch of a record; `x` (a contiguous f32 device image batch) for a record of ``_plan``, which holds none."""
+        t, o, l = (v.data_ptr() if v is not None else None for v in (terms, outs, loss))
+        ws = run["ws"]
+        if x is None:
+            x = run["x"]
+        else:
+            self._check(x)
+            if x.shape[0] != run["n"] or x.dtype != torch.float32 or not x.is_contiguous() or x.device != ws.device:
+                raise ValueError(f"ChestPredictor: the plan was built for {run['n']} contiguous f32 images on {ws.device}")
+        self._ran(run)
         run["lib"].resnet_fwd(ctypes.byref(run["args"]), run["n"], x.data_ptr(), ws.data_ptr(), ws.numel(), t, o, l,
                               torch.cuda.current_stream(x.device).cuda_stream)
 
@@ -317,7 +364,7 @@ class ChestPredictor(_AnticausalPredictor):
         a forward on it (``finding`` = 0: the trunk does not see it) runs first."""
         if x is not None:
             self._outputs({"x": x, "finding": torch.zeros(x.shape[0], 1)})
-        ws, shape = self.__dict__.get("_ws"), self.__dict__.get("_ws_shape")
+        ws, shape = self.__dict__.get("_ws_last"), self.__dict__.get("_ws_shape")
         if ws is None or shape is None:
             raise RuntimeError("ChestPredictor.trunk_activations: no forward has run yet")
         lib = _lib.load()
@@ -336,6 +383,6 @@ class ChestPredictor(_AnticausalPredictor):
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k not in ("_ws", "_ws_token", "_ws_shape", "_rt"):  # runtime workspaces and weight images: rebuilt on first use
+            if k not in ("_ws", "_ws_last", "_ws_token", "_ws_shape", "_rt"):  # runtime workspaces and weight images: rebuilt on first use
                 new.__dict__[k] = _copy.deepcopy(v, memo)
         return new

@@ -1157,6 +1157,12 @@ int cgen_lagrange_step(const cgen_lagrange_step_args* a, cgen_stream_t);
 
 /* Philox normal fill (f32 contiguous) -- exposed for tests of the in-kernel generator */
 int cgen_philox_normal(float* out, int64_t count, const uint64_t* rng, uint32_t stream_id, cgen_stream_t);
+/* Philox uniform fill (f32 contiguous): out[i] = u01(word (i & 3) of the 4 x 32 bits of (seed, offset, stream_id, i >> 2)), with
+ * u01(r) = ((r >> 8) + 0.5) 2^-24 -- open at both ends, so log(-log u) is finite.  {seed, offset} are read from `rng` when the
+ * kernel runs and are not advanced; plain stores, no atomics: reruns are bit-identical.  count == 0 returns CGEN_OK before any
+ * device work.  PgmCounterfactual.run(rng=) fills the Gumbel-max uniforms of cgen_pgm_counterfactual with it, stream id 989 + k
+ * for a PGM's k-th Gumbel-max mechanism (989 .. 996 are reserved for that; the table of taken ids is in csrc/common.h). */
+int cgen_philox_uniform(float* out, int64_t count, const uint64_t* rng, uint32_t stream_id, cgen_stream_t stream);
 /* rng[1] += inc (device-side counter bump so graph replays draw fresh noise) */
 int cgen_rng_advance(uint64_t* rng, uint64_t inc, cgen_stream_t);
 

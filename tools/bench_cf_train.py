@@ -3,14 +3,15 @@
 before it -- ``DSCM.forward`` under autograd (its NaN check and ``.item()`` syncs included) + ``backward`` + ``clip_grad_norm_`` + two
 ``torch.optim.AdamW`` (the multiplier's with ``maximize=True``) + the clamp + a Python EMA loop -- on the same card, in the same run,
 the two paths alternated.  morphomnist and ukbb192 at B = 32, f32 engine, random weights (the recipe of oracle/fullsize_recipe),
-fixed counterfactual parents on both sides (the parent SCM is outside both timings).
+fixed counterfactual parents on both sides (the parent SCM is outside both timings).  ``--presets mimic192`` adds mimic's cell: the
+mimic192 HVAE with ``ChestPredictor`` (constructed directly: ``make_predictor`` keeps its answer for mimic) on ``ChestPGM``'s variables.
 
 Method: warm-up steps, then HIP events around STEPS consecutive steps, RUNS times per path with the paths taking turns; the
 median and the spread (min .. max) are printed, with ABOUT how many kernels a replayed step has (the engine's launch counter over
 the eager first step plus the step's own library launches: torch's few small kernels -- copies, the scalar heads -- are not counted),
 and one JSON line stamped with the tree hash.  The claim to check is "below the host composition in every run", not a ratio.
 
-    python tools/bench_cf_train.py [--steps 20] [--warmup 5] [--runs 3] [--presets morphomnist,ukbb192]
+    python tools/bench_cf_train.py [--steps 20] [--warmup 5] [--runs 3] [--presets morphomnist,ukbb192[,mimic192]]
 """
 import argparse
 import copy
@@ -47,6 +48,8 @@ def variables(preset, g):
         return {"thickness": torch.rand(B, 1, generator=g) * 1.6 - 0.8, "intensity": torch.rand(B, 1, generator=g) * 1.6 - 0.8, "digit": oh}
     r = lambda: torch.rand(B, 1, generator=g) * 1.6 - 0.8  # noqa: E731
     b = lambda: (torch.rand(B, 1, generator=g) < 0.5).float()  # noqa: E731
+    if preset == "mimic192":
+        return {"age": r(), "race": torch.nn.functional.one_hot(torch.randint(0, 3, (B,), generator=g), 3).float(), "sex": b(), "finding": b()}
     return {"mri_seq": b(), "brain_volume": r(), "ventricle_volume": r(), "age": r(), "sex": b()}
 
 
@@ -64,11 +67,17 @@ def build(preset):
     x, _ = R.inputs(hp, B)
     g = torch.Generator().manual_seed(3)
     obs, cf = variables(preset, g), variables(preset, g)
-    parents = list(obs) if preset == "morphomnist" else ["mri_seq", "brain_volume", "ventricle_volume", "sex"]
+    parents = list(obs) if preset in ("morphomnist", "mimic192") else ["mri_seq", "brain_volume", "ventricle_volume", "sex"]
     assert sum(v.shape[1] for k, v in obs.items() if k in parents) == hp.context_dim, (preset, hp.context_dim)
     args = SimpleNamespace(**{**vars(hp), "parents_x": parents, "dataset": preset, "lmbda_init": 0.8, "elbo_constraint": 2.0, "damping": 10.0,
                               "grad_skip": 1e9, "ema_rate": EMA_RATE})
-    pred = predictor.make_predictor(SimpleNamespace(dataset=preset, input_channels=hp.input_channels, input_res=hp.input_res, std_fixed=0.0))
+    pargs = SimpleNamespace(dataset=preset, input_channels=hp.input_channels, input_res=hp.input_res, std_fixed=0.0)
+    if preset == "mimic192":
+        from causal_gen_amd.predictor_resnet import ChestPredictor
+
+        pred = ChestPredictor(pargs)
+    else:
+        pred = predictor.make_predictor(pargs)
     cf = {k: v.cuda() for k, v in cf.items()}
     model = dscm.DSCM(args, FixedPGM(cf), pred, m.eval()).cuda()
     for p in m.parameters():
@@ -90,7 +99,7 @@ def host_step_fn(model, args, batch):
     def step():
         opt.zero_grad(set_to_none=True)
         lag.zero_grad(set_to_none=True)
-        out = model(batch, {"thickness": None}, elbo_fn, cf_particles=1)
+        out = model(batch, {"thickness": None}, elbo_fn, cf_particles=1)  # (FixedPGM answers whatever the intervention is)
         if torch.isnan(out["loss"]):
             return
         out["loss"].sum().backward()
@@ -119,7 +128,10 @@ def device_step_fn(model, args, batch, cf):
     before = eng.launches
     step.step(x, pa, cf_pa, cf)  # eager, then captured: the launch counter saw the step twice
     tail = 2 + len(step.ranges) + 2
-    kernels = (eng.launches - before) // 2 + 2 + 2 + 1 + tail  # engine passes + predictor fwd / bwd + non-finite x2 + Lagrangian + tail
+    # the CNN heads are one launch each way; ChestPredictor's two plans (csrc/predictor_resnet.inc rn_forward / rn_backward, counted
+    # launch by launch with one kernel per conv) are 84 forward with the sum of the terms and 90 backward
+    pred = 84 + 90 if type(step.pred).__name__ == "ChestPredictor" else 2
+    kernels = (eng.launches - before) // 2 + pred + 2 + 1 + tail  # engine passes + predictor fwd / bwd + non-finite x2 + Lagrangian + tail
     return (lambda: step.step(x, pa, cf_pa, cf)), step, kernels
 
 
