@@ -5,11 +5,14 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CGEN_LIB") or os.path.join(_HERE, "libcgen_hip.so")  # (CGEN_LIB: another build of the same ABI, for A/B runs)
 
+OK, EINVAL, ELAUNCH, EUNSUPPORTED = 0, -1, -2, -3
 F32, F16, F32S = 0, 1, 2
 DMOL_LOW_BIT = 0x100  # OR-ed into the dtype of cgen_dmol_nll_fwd/bwd: the reference's low_bit=True branch (dmol.py:52-60)
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 UNARY_LEAKY_RELU, UNARY_CLAMP_MIN, UNARY_ADD = 3, 4, 5
 MAX_SEG = 4
+BLOCK3_PLAN_INTS, BLOCK4_PLAN_INTS, WGRAD_PLAN_INTS = 24, 16, 24  # int32 entries of the cgen_*_plan / _plan_record outputs
+PRED_PLAN_LAUNCHES, PRED_PLAN_FIELDS = 13, 8  # cgen_predictor_tiled_plan: records of a full plan, int32 fields per record
 
 
 class View(C.Structure):
@@ -215,8 +218,9 @@ RESNET_CONVS, RESNET_SITES = 20, 18
 
 i32, i64, u32, u64, f32, vp = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p
 
-# name -> argtypes (all return int unless listed in _RESTYPES).  Kept in lock-step with include/cgen_hip.h;
-# tests/test_abi.py parses the header and checks every declared symbol is exported and bound here.
+# name -> argtypes (all return int unless listed in _RESTYPES).  Kept in lock-step with include/cgen_hip.h:
+# tests/test_abi_mirror.py holds every prototype, every struct of STRUCTS (below) and every constant of this module to the
+# header as gcc reads it; tests/test_abi.py checks that every declared symbol is exported and bound here.
 PROTOTYPES = {
     "cgen_version": [],
     "cgen_h16_format": [],
@@ -354,6 +358,37 @@ _NOCHECK = {"cgen_version", "cgen_h16_format", "cgen_last_error", "cgen_conv2d_w
 
 class WgradBatchLaunch(C.Structure):
     _fields_ = [("ncf", C.c_int32), ("ks", C.c_int32), ("lds_bytes", C.c_int32), ("nblocks", C.c_int32), ("blocks_offset", C.c_int64)]
+
+
+# C struct name -> its mirror, every struct of the header: a new struct is one more line here
+STRUCTS = {
+    "cgen_view": View,
+    "cgen_conv_args": ConvArgs,
+    "cgen_block3_out": Block3Out,
+    "cgen_block3_args": Block3Args,
+    "cgen_block4_args": Block4Args,
+    "cgen_wgrad_args": WgradArgs,
+    "cgen_wgrad_batch_launch": WgradBatchLaunch,
+    "cgen_wprep_desc": WprepDesc,
+    "cgen_wred_desc": WredDesc,
+    "cgen_wred_item": WredItem,
+    "cgen_augment_args": AugmentArgs,
+    "cgen_latent_tail_bwd_args": LatentTailArgs,
+    "cgen_latent_tail_fwd_args": LatentTailFwdArgs,
+    "cgen_dgauss_head_args": DgaussHeadArgs,
+    "cgen_pred_head": PredHead,
+    "cgen_pred_train_head": PredTrainHead,
+    "cgen_resnet_args": ResnetArgs,
+    "cgen_resnet_train_args": ResnetTrainArgs,
+    "cgen_mlp_train_head": MlpTrainHead,
+    "cgen_metric_var": MetricVar,
+    "cgen_pgm_mech": PgmMech,
+    "cgen_pgm_pre": PgmPre,
+    "cgen_pgm_cf_args": PgmCfArgs,
+    "cgen_adamw_args": AdamwArgs,
+    "cgen_cf_lagrange_args": CfLagrangeArgs,
+    "cgen_lagrange_step_args": LagrangeStepArgs,
+}
 
 
 class CgenError(RuntimeError):

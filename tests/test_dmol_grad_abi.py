@@ -1,15 +1,10 @@
 """The DMoL decode backward entry points without a GPU: argument validation happens before any launch, and the gfx950 code
 object holds both storage instances of the two new kernels with no scratch and no spilled registers."""
-import glob
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-from conftest import ROOT
+import codeobj
 
 
 def _view(c):
@@ -57,27 +52,13 @@ def test_dmol_backward_entry_points_reject_bad_arguments():
 
 
 def test_dmol_backward_kernels_have_no_scratch_and_no_spills():
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    so = os.path.join(ROOT, "causal-gen_amd", "libcgen_hip.so")
-    if not (os.path.exists(objdump) and os.path.exists(readelf) and os.path.exists(so)):
-        pytest.skip("llvm tools or the built library are missing")
     seen = {}
-    with tempfile.TemporaryDirectory() as d:
-        shutil.copy(so, d)
-        subprocess.run([objdump, "--offloading", os.path.join(d, "libcgen_hip.so")], check=True, capture_output=True)
-        bundles = glob.glob(os.path.join(d, "*gfx950*"))
-        assert bundles, "no gfx950 code object in the library"
-        for b in bundles:
-            notes = subprocess.run([readelf, "--notes", b], check=True, capture_output=True, text=True).stdout
-            for m in re.finditer(r"\.name:\s+(\S+)(.*?)\.wavefront_size", notes, re.S):
-                name, body = m.group(1), m.group(2)
-                k = re.search(r"(dmol_decode_bwd_kernel|cf_dmol_bwd_kernel)I([ft])", name)
-                if not k:
-                    continue
-                seen[k.group(1) + ("<float>" if k.group(2) == "f" else "<h16_t>")] = name
-                scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
-                sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", body)
-                assert scratch == 0, (name, scratch)
-                assert sp is None or int(sp.group(1)) == 0, (name, sp.group(1))
+    for name, scratch, spills in codeobj.kernels():
+        k = re.search(r"(dmol_decode_bwd_kernel|cf_dmol_bwd_kernel)I([ft])", name)
+        if not k:
+            continue
+        seen[k.group(1) + ("<float>" if k.group(2) == "f" else "<h16_t>")] = name
+        assert scratch == 0, (name, scratch)
+        assert spills == 0, (name, spills)
     assert sorted(seen) == ["cf_dmol_bwd_kernel<float>", "cf_dmol_bwd_kernel<h16_t>", "dmol_decode_bwd_kernel<float>",
                             "dmol_decode_bwd_kernel<h16_t>"], sorted(seen)

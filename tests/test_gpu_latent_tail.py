@@ -297,21 +297,6 @@ def test_declined_cases_return_the_error_code():
     torch.cuda.synchronize()
 
 
-def test_struct_layout_matches_header():
-    import os
-    import subprocess
-    import tempfile
-
-    from conftest import ROOT
-
-    prog = '#include <stdio.h>\n#include "cgen_hip.h"\nint main(void) { printf("%zu\\n", sizeof(cgen_latent_tail_bwd_args)); return 0; }\n'
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        assert int(subprocess.check_output([exe])) == C.sizeof(_lib().LatentTailArgs)
-
-
 # ----------------------------------------------------------------------------- model level
 def _small_hp(**over):
     from causal_gen_amd.hps import setup_hparams

@@ -289,21 +289,6 @@ def test_supported_answers_without_a_gpu_and_declined_calls_return_the_error_cod
             assert b"cgen_latent_tail_fwd" in lib.cdll.cgen_last_error()
 
 
-def test_struct_layout_matches_header():
-    import os
-    import subprocess
-    import tempfile
-
-    from conftest import ROOT
-
-    prog = '#include <stdio.h>\n#include "cgen_hip.h"\nint main(void) { printf("%zu\\n", sizeof(cgen_latent_tail_fwd_args)); return 0; }\n'
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        assert int(subprocess.check_output([exe])) == C.sizeof(_lib().LatentTailFwdArgs)
-
-
 # ----------------------------------------------------------------------------- model level
 def _small_hp(**over):
     from causal_gen_amd.hps import setup_hparams

@@ -316,21 +316,6 @@ def test_backward_declines_a_split_count_that_is_not_the_plan():
     assert lib._raw_cgen_dgauss_head_bwd(C.byref(t), None) == EUNSUPPORTED
 
 
-def test_struct_layout_matches_header():
-    import os
-    import subprocess
-    import tempfile
-
-    from conftest import ROOT
-
-    prog = '#include <stdio.h>\n#include "cgen_hip.h"\nint main(void) { printf("%zu\\n", sizeof(cgen_dgauss_head_args)); return 0; }\n'
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        assert int(subprocess.check_output([exe])) == C.sizeof(_lib().DgaussHeadArgs)
-
-
 # ----------------------------------------------------------------------------- f64
 K0, K1 = 0.79788456080286535588, 0.044715
 

@@ -1,11 +1,9 @@
-"""The parent-SCM entry points without a GPU: exported, declared and bound at ABI 411, the mechanism record's layout is gcc's, the
-workspace query follows the slot counts, every entry rejects bad arguments before anything is launched with a message naming the
-field, and PgmTrainStep's record builder refuses a PGM the kernel does not serve."""
+"""The parent-SCM entry points without a GPU: exported, declared and bound at ABI 411, eight mechanism records fit the
+kernel-argument segment, the workspace query follows the slot counts, every entry rejects bad arguments before anything is launched
+with a message naming the field, and PgmTrainStep's record builder refuses a PGM the kernel does not serve."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
@@ -51,25 +49,11 @@ def test_symbols_exported_declared_and_bound_at_abi_411():
     assert "typedef struct cgen_pgm_mech {" in hdr
 
 
-def test_mechanism_record_layout_matches_gcc():
+def test_mechanism_records_fit_the_kernel_argument_segment():
+    """(the record's layout and the constants against the header: tests/test_abi_mirror.py)"""
     from causal_gen_amd import _lib
 
-    fields = [f for f, _ in _lib.PgmMech._fields_]
-    consts = ("CGEN_PGM_MAX_MECH", "CGEN_PGM_MAX_WIDTH", "CGEN_PGM_MAX_HIDDEN", "CGEN_PGM_MAX_BINS", "CGEN_PGM_MAX_CLS", "CGEN_PGM_ROWS",
-              "CGEN_PGM_BERNOULLI", "CGEN_PGM_CATEGORICAL", "CGEN_PGM_SPLINE", "CGEN_PGM_AFFINE", "CGEN_PGM_GUMBEL_MAX",
-              "CGEN_PGM_LEAKY_RELU", "CGEN_PGM_GELU", "CGEN_PGM_SIGMOID")
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "cgen_hip.h"\nint main(void) { printf("%zu", sizeof(cgen_pgm_mech));\n'
-    prog += "".join('printf(" %%zu", offsetof(cgen_pgm_mech, %s));\n' % f for f in fields)
-    prog += "".join('printf(" %%d", (int)%s);\n' % c for c in consts) + "return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    A = _lib.PgmMech
-    assert got[:1 + len(fields)] == [C.sizeof(A)] + [getattr(A, f).offset for f in fields]
-    assert got[1 + len(fields):] == [getattr(_lib, c[len("CGEN_"):]) for c in consts]
-    assert C.sizeof(A) * _lib.PGM_MAX_MECH < 3500  # eight records travel by value in a 4 KiB kernel-argument segment
+    assert C.sizeof(_lib.PgmMech) * _lib.PGM_MAX_MECH < 3500  # eight records travel by value in a 4 KiB kernel-argument segment
 
 
 def test_workspace_follows_the_slot_counts():

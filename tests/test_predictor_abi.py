@@ -1,17 +1,13 @@
 """Anticausal predictors without a GPU: argument validation before any launch, a clean gfx950 code object, and the module
 surface (reference state-dict names, the f64 oracle against the reference CNN's own outputs)."""
-import glob
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 from types import SimpleNamespace
 
 import pytest
 import torch
 
-from conftest import ROOT, load_golden
+import codeobj
+from conftest import load_golden
 from predictor_ref import cnn_ref
 
 
@@ -66,28 +62,14 @@ def test_predictor_entry_points_reject_bad_records():
 
 
 def test_predictor_kernels_have_no_scratch_and_no_spills():
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    so = os.path.join(ROOT, "causal-gen_amd", "libcgen_hip.so")
-    if not (os.path.exists(objdump) and os.path.exists(readelf) and os.path.exists(so)):
-        pytest.skip("llvm tools or the built library are missing")
     seen = set()
-    with tempfile.TemporaryDirectory() as d:
-        shutil.copy(so, d)
-        subprocess.run([objdump, "--offloading", os.path.join(d, "libcgen_hip.so")], check=True, capture_output=True)
-        bundles = glob.glob(os.path.join(d, "*gfx950*"))
-        assert bundles, "no gfx950 code object in the library"
-        for b in bundles:
-            notes = subprocess.run([readelf, "--notes", b], check=True, capture_output=True, text=True).stdout
-            for m in re.finditer(r"\.name:\s+(\S+)(.*?)\.wavefront_size", notes, re.S):
-                name, body = m.group(1), m.group(2)
-                k = re.search(r"(predictor_kernelILb[01]ELb[01]E|pred_sum_kernel)", name)
-                if not k:
-                    continue
-                seen.add(k.group(1))
-                scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
-                sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", body)
-                assert scratch == 0, (name, scratch)
-                assert sp is None or int(sp.group(1)) == 0, (name, sp.group(1))
+    for name, scratch, spills in codeobj.kernels():
+        k = re.search(r"(predictor_kernelILb[01]ELb[01]E|pred_sum_kernel)", name)
+        if not k:
+            continue
+        seen.add(k.group(1))
+        assert scratch == 0, (name, scratch)
+        assert spills == 0, (name, spills)
     assert len(seen) == 5, sorted(seen)
 
 

@@ -1,16 +1,11 @@
 """The tiled placement of the anticausal predictors without a GPU: support and workspace queries against a restatement of the
 stack geometry, argument validation before any launch, and a gfx950 code object whose new kernels use no scratch."""
 import ctypes
-import glob
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-from conftest import ROOT
+import codeobj
 
 SHAPES = [(1, 192, 16), (1, 32, 8), (3, 40, 8), (1, 8, 8), (1, 66, 32)]  # (c, res, width)
 
@@ -121,28 +116,14 @@ def test_tiled_entry_points_reject_bad_arguments_before_launch():
 
 
 def test_tiled_kernels_have_no_scratch_and_no_spills():
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    so = os.path.join(ROOT, "causal-gen_amd", "libcgen_hip.so")
-    if not (os.path.exists(objdump) and os.path.exists(readelf) and os.path.exists(so)):
-        pytest.skip("llvm tools or the built library are missing")
     seen = {}
-    with tempfile.TemporaryDirectory() as d:
-        shutil.copy(so, d)
-        subprocess.run([objdump, "--offloading", os.path.join(d, "libcgen_hip.so")], check=True, capture_output=True)
-        bundles = glob.glob(os.path.join(d, "*gfx950*"))
-        assert bundles, "no gfx950 code object in the library"
-        for b in bundles:
-            notes = subprocess.run([readelf, "--notes", b], check=True, capture_output=True, text=True).stdout
-            for m in re.finditer(r"\.name:\s+(\S+)(.*?)\.wavefront_size", notes, re.S):
-                name, body = m.group(1), m.group(2)
-                k = re.search(r"(ptile_conv_fwd|ptile_conv_bwd|ptile_stem_bwd|ptile_tail)", name)
-                if not k:
-                    continue
-                seen[k.group(1)] = seen.get(k.group(1), 0) + 1
-                scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
-                sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", body)
-                assert scratch == 0, (name, scratch)
-                assert sp is None or int(sp.group(1)) == 0, (name, sp.group(1))
+    for name, scratch, spills in codeobj.kernels():
+        k = re.search(r"(ptile_conv_fwd|ptile_conv_bwd|ptile_stem_bwd|ptile_tail)", name)
+        if not k:
+            continue
+        seen[k.group(1)] = seen.get(k.group(1), 0) + 1
+        assert scratch == 0, (name, scratch)
+        assert spills == 0, (name, spills)
     # stem 2 strides x 4 channel blockings; 3x3 forward (stride 1, stride 2, stride 2 + pool) x 2 tile sizes x 4; 3x3 data
     # gradient 3 x 4; stem data gradient per stride; tail forward / backward
     assert seen == {"ptile_conv_fwd": 8 + 24, "ptile_conv_bwd": 12, "ptile_stem_bwd": 2, "ptile_tail": 2}, seen

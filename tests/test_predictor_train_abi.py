@@ -1,16 +1,13 @@
-"""Training of the anticausal predictors without a GPU: the three entry points are exported, declared and bound at ABI 411, the
-head record's layout is gcc's, every entry rejects bad arguments before anything is launched with a message naming the cause,
-the workspace query follows the stack geometry, and the training kernels of the gfx950 code object use no scratch."""
+"""Training of the anticausal predictors without a GPU: the three entry points are exported, declared and bound at ABI 411, four
+head records fit the kernel-argument segment, every entry rejects bad arguments before anything is launched with a message naming
+the cause, the workspace query follows the stack geometry, and the training kernels of the gfx950 code object use no scratch."""
 import ctypes as C
-import glob
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
+import codeobj
 from conftest import ROOT
 
 ENTRIES = ("cgen_predictor_train_workspace", "cgen_predictor_train_fwd", "cgen_predictor_train_bwd")
@@ -52,20 +49,11 @@ def test_symbols_exported_declared_and_bound_at_abi_411():
     assert "typedef struct cgen_pred_train_head {" in hdr
 
 
-def test_head_record_layout_matches_gcc():
+def test_head_records_fit_the_kernel_argument_segment():
+    """(the record's layout against the header: tests/test_abi_mirror.py)"""
     from causal_gen_amd import _lib
 
-    fields = ("hd", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked", "gw", "gb", "ggamma", "gbeta")
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "cgen_hip.h"\nint main(void) { printf("%zu", sizeof(cgen_pred_train_head));\n'
-    prog += "".join('printf(" %%zu", offsetof(cgen_pred_train_head, %s));\n' % f for f in fields) + "return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
-        open(src, "w").write(prog)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        got = [int(v) for v in subprocess.check_output([exe]).split()]
-    A = _lib.PredTrainHead
-    assert got == [C.sizeof(A)] + [getattr(A, f).offset for f in fields]
-    assert C.sizeof(A) * _lib.PRED_MAX_HEADS < 3500  # four records travel by value in a 4 KiB kernel-argument segment
+    assert C.sizeof(_lib.PredTrainHead) * _lib.PRED_MAX_HEADS < 3500  # four records travel by value in a 4 KiB kernel-argument segment
 
 
 def _stack_floats(res, width):
@@ -185,28 +173,14 @@ def test_python_step_rejects_bad_setups_before_any_device_work():
 
 
 def test_training_kernels_have_no_scratch_and_no_spills():
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    so = os.path.join(ROOT, "causal-gen_amd", "libcgen_hip.so")
-    if not (os.path.exists(objdump) and os.path.exists(readelf) and os.path.exists(so)):
-        pytest.skip("llvm tools or the built library are missing")
     seen = {}
-    with tempfile.TemporaryDirectory() as d:
-        shutil.copy(so, d)
-        subprocess.run([objdump, "--offloading", os.path.join(d, "libcgen_hip.so")], check=True, capture_output=True)
-        bundles = glob.glob(os.path.join(d, "*gfx950*"))
-        assert bundles, "no gfx950 code object in the library"
-        for b in bundles:
-            notes = subprocess.run([readelf, "--notes", b], check=True, capture_output=True, text=True).stdout
-            for m in re.finditer(r"\.name:\s+(\S+)(.*?)\.wavefront_size", notes, re.S):
-                name, body = m.group(1), m.group(2)
-                k = re.search(r"\d+(ptrain_[a-z0-9_]+?)(?:I|E)", name)
-                if not k:
-                    continue
-                seen[k.group(1)] = seen.get(k.group(1), 0) + 1
-                scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
-                sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", body)
-                assert scratch == 0, (name, scratch)
-                assert sp is None or int(sp.group(1)) == 0, (name, sp.group(1))
+    for name, scratch, spills in codeobj.kernels():
+        k = re.search(r"\d+(ptrain_[a-z0-9_]+?)(?:I|E)", name)
+        if not k:
+            continue
+        seen[k.group(1)] = seen.get(k.group(1), 0) + 1
+        assert scratch == 0, (name, scratch)
+        assert spills == 0, (name, spills)
     # the 7x7 and the 3x3 form of the forward conv and of the weight gradient, the forward and backward form of the tail's output
     # stage; one of everything else
     assert seen == {"ptrain_conv_fwd": 2, "ptrain_bn_fwd": 1, "ptrain_tail_fc0": 1, "ptrain_tail_bn": 1, "ptrain_tail_out": 2,
